@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: client-rounds/s of the federated round on MI355X (BASELINE.json configs 2-5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR] [...]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
+
+A plain run does what the headline figure needs and nothing else: it sets up, settles the device
+clocks, runs W warm-up rounds, times K rounds, writes the last timed round's outputs if
+``--dump-outputs DIR`` is given (dump_outputs below: ``DIR/<name>.npy``) and prints the line.
+``--full`` adds, after the timed rounds, everything else this file measures: the CPU baselines, the
+fs_aggregate launch timing, the FedAMW leg of config 2 and the config 1/3/4/5 legs.
 
 Launch.  ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process
 starts N worker processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per
@@ -29,15 +35,17 @@ Extra objects on the JSON line:
                 bytes per launch and ``mfma_busy`` = the MFMA pipe's busy fraction, both from
                 profiles/traffic_local_train_<config>.json, used only when its ``source_rev``
                 equals the revision of the kernel sources being run (_lib.source_revision()).
-  cpu_baseline  the CPU oracle (oracle/fedsim_oracle.py, numpy restatement of the reference
+  aggregate     (--full) fs_aggregate's ms per launch and algorithmic GB/s: 20 launches back to back after
+                the timed rounds (aggregate_timing).
+  cpu_baseline  (--full) the CPU oracle (oracle/fedsim_oracle.py, numpy restatement of the reference
                 round) timed on this host (rank 0, N = 1 only) on a bounded sample.
-  fedamw        (config 2, one GPU) the other half of config 2 -- "FedAvg vs optimal mixture
+  fedamw        (--full, config 2, one GPU) the other half of config 2 -- "FedAvg vs optimal mixture
                 weights": FedAMW rounds on the same clients plus 128 validation rows each.
-  config1       (default run, one GPU) exp.py's FedAMW on 10 chained a9a-shaped Dirichlet(0.01)
+  config1       (--full, config 2, one GPU) exp.py's FedAMW on 10 chained a9a-shaped Dirichlet(0.01)
                 clients, D = 2000, C = 2, R = 100: ms per round, the bin p-solve's us per step, and
                 the numpy oracle's round on the host.
   config4 / config3 / config5
-                (default run) the >= 1000-client BASELINE configs, each with its own rounds,
+                (--full, config 2) the >= 1000-client BASELINE configs, each with its own rounds,
                 ms_per_round, client-rounds/s, roofline and cpu_baseline; config 5 adds the
                 p-solve's steps/s, bytes/s and PMC traffic.
 Config 5 is BASELINE's 1000 clients over all GPUs (strong scaling: 1000/N clients per GPU);
@@ -71,7 +79,7 @@ PRESETS = {
     5: dict(algo='fedamw', clients=1000, rows=128, D=16384, C=10, test=10000, shape='a9a'),
 }
 STRONG = {5}
-# the extra legs of the default run: (config, timed rounds, warmup rounds)
+# the extra legs of the --full run: (config, timed rounds, warmup rounds)
 LEGS = ((4, 10, 10), (3, 5, 2), (5, 2, 1))     # (config, timed rounds, warm-up rounds)
 # CPU-sample budget floors per leg: config 3's whole round (1,000 clients) fits in ~60 % of 6 s on
 # the box's 16 host threads, so its baseline is a measured round instead of an extrapolation
@@ -98,13 +106,22 @@ def parse(argv=None):
     ap.add_argument('--shape', choices=['a9a', 'covtype'])
     ap.add_argument('--rounds', type=int, help="the algorithm's `round` argument (LR schedule; FedAMW's inner "
                                                 'p-SGD epochs per round); default 100 = the reference default')
-    ap.add_argument('--cpu-seconds', type=float, default=10.0, help='budget of the headline CPU baseline sample')
-    ap.add_argument('--leg-cpu-seconds', type=float, default=3.0, help='budget of each extra leg\'s CPU sample')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure everything beside the headline figure: the CPU '
+                         'baselines, the fs_aggregate launch timing, the FedAMW leg of config 2 and the config '
+                         '1/3/4/5 legs (the --no-* flags below drop single parts of it); without it the run sets '
+                         'up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed round computed to DIR/<name>.npy '
+                         '(float32 / float64; see dump_outputs)')
+    ap.add_argument('--cpu-seconds', type=float, default=10.0,
+                    help='--full: budget of the headline CPU baseline sample')
+    ap.add_argument('--leg-cpu-seconds', type=float, default=3.0, help='--full: budget of each extra leg\'s CPU sample')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
     ap.add_argument('--host-shuffle', action='store_true', help='replay shuffles on host threads, not the GPU')
-    ap.add_argument('--no-fedamw-leg', action='store_true', help='skip the FedAMW object of the config-2 line')
-    ap.add_argument('--fedamw-rounds', type=int, default=2, help='timed FedAMW rounds of the config-2 leg')
-    ap.add_argument('--no-legs', action='store_true', help='skip the config 3/4/5 objects of the default line')
+    ap.add_argument('--no-fedamw-leg', action='store_true', help='--full without the FedAMW object of the config-2 line')
+    ap.add_argument('--fedamw-rounds', type=int, default=2, help='--full: timed FedAMW rounds of the config-2 leg')
+    ap.add_argument('--no-legs', action='store_true', help='--full without the config 1/3/4/5 objects of the line')
     ap.add_argument('--train-form', choices=['auto', 'split', 'pair', 'teams', 'pipe'], default='auto',
                     help="fs_tuning.train_form / split_teams / split_pipe: the local-training kernel form for parallel "
                          "clients (A/B runs)")
@@ -640,9 +657,12 @@ def config1_leg(dev, rounds=10, warmup=2, cpu_budget=3.0):
 
 
 def run_workload(wl, ws, rank, dev, steps, warmup, R_arg, cpu_seconds, host_shuffle=False, custom=False,
-                 fedamw_leg_rounds=0):
+                 fedamw_leg_rounds=0, full=True, dump_dir=None):
     """One BASELINE workload: set up (untimed), ``warmup`` rounds, ``steps`` timed rounds
-    bracketed by barrier + synchronize, max over ranks.  Returns the workload's line fields."""
+    bracketed by barrier + synchronize, max over ranks.  Returns the workload's line fields.
+    ``full``: also the measurements that take runs of their own after the timed rounds (the
+    fs_aggregate launch timing; the FedAMW leg and the CPU baseline where asked for).
+    ``dump_dir``: rank 0 writes the last timed round's outputs there (dump_outputs)."""
     import torch
     import torch.distributed as tdist
     from fedamw_amd import data as fdata
@@ -707,7 +727,9 @@ def run_workload(wl, ws, rank, dev, steps, warmup, R_arg, cpu_seconds, host_shuf
         el = float(t.item())
     lt_ms = phase_ms(fed.events, 'train')
     tr, tl, ta = fed.results()
-    agg = aggregate_timing(fed, wl)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, fed, (tr, tl, ta))
+    agg = aggregate_timing(fed, wl) if full else None
     n_rows = int(fed.feats.rows)
     alg_bytes = 4.0 * E * n_rows * wl['D'] + 8.0 * E * n_rows + 8.0 * N_loc * wl['C'] * wl['D']
     achieved = alg_bytes / (lt_ms * 1e-3) / 1e9 if lt_ms else float('nan')
@@ -738,11 +760,12 @@ def run_workload(wl, ws, rank, dev, steps, warmup, R_arg, cpu_seconds, host_shuf
                      'form': 'pair' if fed.trainer.pair else ('teams' if fed.trainer.teams else
                                                               ('pipe' if fed.trainer.pipe else
                                                                ('split' if fed.trainer.G > 1 else 'single')))},
-        'aggregate': agg,
         'final_test_acc': float(ta[fed.t - 1]),
         'device_settle_ms': settled,
         'device_settle_kind': settle_kind,
     }
+    if agg is not None:
+        out['aggregate'] = agg
     if fedamw:
         nv = fed.mixture.nv
         p_steps = R * ((nv + 15) // 16)
@@ -774,6 +797,35 @@ def run_workload(wl, ws, rank, dev, steps, warmup, R_arg, cpu_seconds, host_shuf
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_CLIENT_BYTES = 32 << 20     # --dump-outputs: budget of the sampled client models (all files < 64 MB)
+
+
+def dump_outputs(path, fed, results):
+    """--dump-outputs: what the timed path (Federation.round + results) handed back after its last
+    timed round, one ``<name>.npy`` per array, so that two builds run with the same arguments can
+    be compared output for output (the inputs are seeded: data by 1000 + rank, torch by 100, the
+    settle's shuffles by a private generator):
+      W_global     [C, D] float32   the global model after the last timed round
+      train_loss / test_loss / test_acc   [warmup + steps] float32   the histories results() returns
+      p            [N] float32      FedAMW only: the learned mixture weights
+      W_clients    [k, C, D] float32   the last round's trained client models (this rank's), all of
+                   them when they fit DUMP_CLIENT_BYTES, else a fixed seeded sample of k clients
+      W_clients_index   [k] float64   which clients (positions among this rank's) W_clients holds"""
+    os.makedirs(path, exist_ok=True)
+    tr, tl, ta = results
+    t, D = fed.t, fed.D
+    arrays = {'W_global': fed.W_g[:, :D], 'train_loss': tr[:t], 'test_loss': tl[:t], 'test_acc': ta[:t]}
+    if fed.mixture is not None:
+        arrays['p'] = fed.mixture.p[fed.pos_dev] if fed.zshard else fed.mixture.p
+    n = len(fed.mine)
+    k = min(n, max(1, DUMP_CLIENT_BYTES // (4 * fed.C * D)))
+    idx = np.sort(np.random.default_rng(2024).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    arrays['W_clients'] = fed.trainer.W_out[:n][idx.tolist(), :, :D]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(_np(a), dtype=np.float32))
+    np.save(os.path.join(path, 'W_clients_index.npy'), idx.astype(np.float64))
 
 
 def aggregate_timing(fed, wl, reps=20):
@@ -832,11 +884,13 @@ def worker(args):
     wl = {k: getattr(args, k) for k in ('algo', 'clients', 'rows', 'D', 'C', 'test', 'shape')}
     wl['config'] = args.config
     headline = (args.config == 2 and not args.custom)
-    leg_rounds = args.fedamw_rounds if (headline and args.algo == 'fedavg' and ws == 1
+    # everything beside the headline figure runs only under --full
+    no_cpu = args.no_cpu_baseline or not args.full
+    leg_rounds = args.fedamw_rounds if (args.full and headline and args.algo == 'fedavg' and ws == 1
                                         and not args.no_fedamw_leg) else 0
-    cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_seconds
+    cpu_s = 0.0 if no_cpu else args.cpu_seconds
     main = run_workload(wl, ws, rank, dev, args.steps, args.warmup, args.rounds, cpu_s, args.host_shuffle,
-                        args.custom, leg_rounds)
+                        args.custom, leg_rounds, full=args.full, dump_dir=args.dump_outputs)
     out = {
         'metric': 'client-rounds/sec (whole node)',
         'value': main['value'],
@@ -853,15 +907,15 @@ def worker(args):
         'config': dict(workload=main['workload'], **main['config']),
         'dist': dinfo,
         'roofline': main['roofline'],
-        'aggregate': main['aggregate'],
         'final_test_acc': main['final_test_acc'],
         'device_settle_ms': main['device_settle_ms'],
         'device_settle_kind': main['device_settle_kind'],
     }
-    for k in ('fedamw', 'cpu_baseline'):
+    for k in ('aggregate', 'fedamw', 'cpu_baseline'):
         if k in main:
             out[k] = main[k]
-    if headline and not args.no_legs:
+    legs = args.full and headline and not args.no_legs
+    if legs:
         for cfg, k, w in LEGS:
             lw = dict(PRESETS[cfg], config=cfg)
             t0 = time.perf_counter()
@@ -879,7 +933,7 @@ def worker(args):
             if rank == 0:
                 print('bench: config %d leg %.1f s, %.0f client-rounds/s' % (cfg, obj['leg_wall_s'], obj['value']),
                       file=sys.stderr, flush=True)
-    if headline and not args.no_legs and ws == 1:
+    if legs and ws == 1:
         t0 = time.perf_counter()
         obj = config1_leg(dev, cpu_budget=0.0 if args.no_cpu_baseline else args.leg_cpu_seconds)
         obj['leg_wall_s'] = time.perf_counter() - t0

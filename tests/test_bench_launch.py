@@ -110,6 +110,15 @@ def test_defaults_are_config2():
     assert [c for c, _, _ in bench.LEGS] == [4, 3, 5]
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain run measures the headline only; --full (off by default) adds the rest, and
+    --dump-outputs names the directory of the last timed round's arrays."""
+    a = bench.parse(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(['--full', '--dump-outputs', 'somewhere'])
+    assert a.full is True and a.dump_outputs == 'somewhere'
+
+
 def test_cpu_fedamw_round_is_one_whole_oracle_round():
     """bench.cpu_fedamw_round (config 5's measured CPU baseline, round 6): one whole FedAMW round of
     the oracle -- every client's training, the Z GEMM on every validation row, all R x ceil(n_v / 16)
