@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 16
+#define FS_ABI_VERSION 17
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -261,6 +261,26 @@ int fs_local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, con
                    int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * (ABI 17) Local training under nn.MSELoss at ONE output column: train_loop with
+ * type != 'classification' (tools.py:177-215, the criterion of tools.py:183-184) and
+ * num_classes = 1 (utils.py:121, 167).  Arguments as fs_local_train without C, G and the
+ * workspace:
+ *   d_y        [rows] float    target per row (the [n, 1] targets of utils.py:81-82, flattened)
+ *   d_W_start  [ld]            round-start weights;  d_W_out [N][ld]
+ * Per batch b: o_i = phi_i . w;  L = (1/|b|) sum_i (o_i - y_i)^2 [+ mu ||w - w_a||] [+ lam ||w||];
+ * dL/do_i = (2/|b|) (o_i - y_i);  w -= lr (sum_i dL/do_i phi_i + mu (w - w_a)/||w - w_a|| +
+ * lam w/||w||) (tools.py:190-211; a zero norm contributes a zero gradient).  d_loss as
+ * fs_local_train.  One workgroup per client (parallel clients: a grid of N in d_order) or one
+ * workgroup walking the chain; w lives in registers; no cross-workgroup exchange, no spin, no
+ * workspace.  Requires 1 <= B <= 64, ld % 64 == 0, ld <= 16384, E >= 0: anything else returns
+ * FS_EUNSUPPORTED before launching.
+ * ------------------------------------------------------------------------- */
+int fs_local_train_mse(const float* d_phi, int64_t ld, const int64_t* d_row_off, const float* d_y,
+                       const int32_t* d_perms, const int32_t* d_order, int N, int B, int E, float lr, float mu,
+                       int prox, float lam, int reg, int chained, const float* d_W_start, float* d_W_out,
+                       double* d_loss, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Weighted aggregation: d_W_bar = p0*W0 + p1*W1 + ... + p_{N-1}*W_{N-1}, every
  * product and sum rounded separately in that left-to-right order
  * (tools.py:345-350, 372-377, 455-460).  W_j = d_W_all + j*stride, len floats.
@@ -280,6 +300,17 @@ int fs_aggregate(const float* d_W_all, int64_t stride, const float* d_p, int N, 
 int64_t fs_eval_ws_doubles(int n);
 int fs_eval(const float* d_phi, int64_t ld, const int32_t* d_labels, int n, const float* d_W, int C,
             double* d_out, double* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 17) Test evaluation under nn.MSELoss at one output column (tools.py:218-237 with the
+ * criterion of tools.py:223-224): d_out[0] = mean squared error over n rows (per-block fp64
+ * partials, folded in a fixed order as fs_eval's), d_out[1] = 100 * #{y == 0} / n -- the
+ * reference's comp_accuracy (tools.py:82-96) takes the top-1 index of a one-column output,
+ * always 0, and compares it with the float target; that value is reproduced, not improved.
+ * d_y [n] float, d_W [ld]; d_ws needs fs_eval_ws_doubles(n) doubles.
+ * ------------------------------------------------------------------------- */
+int fs_eval_mse(const float* d_phi, int64_t ld, const float* d_y, int n, const float* d_W, double* d_out,
+                double* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * FedAMW mixture step 1: Z[v][c*ldN + n] = sum_d X_val[v][d] * W_n[c][d], where
@@ -316,6 +347,21 @@ int64_t fs_mix_solve_ws_bytes(int N, int C, int Bv);
 int fs_mix_solve(const float* d_Z, const int32_t* d_labels, const int32_t* d_perms, int N, int C,
                  int n_val, int epochs, int Bv, float lr_p, float momentum, float* d_p, float* d_buf,
                  int* d_first, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 17) FedAMW mixture step 2 under nn.MSELoss at one output column (tools.py:441-453
+ * with the criterion of tools.py:421-422; FedAMW_OneShot tools.py:304-316, momentum 0):
+ * d_Z is what fs_mix_z writes at C = 1, [n_val][ldN]; d_y [n_val] float targets.  Per batch:
+ * out_b = sum_n p_n Z[v_b][n];  L = mean_b (out_b - y_b)^2;  grad_n = (2/|b|) sum_b (out_b -
+ * y_b) Z[v_b][n];  buf = first ? grad : momentum * buf + grad;  p -= lr_p * buf.  d_p, d_buf,
+ * d_first, d_perms, the workspace (fs_mix_solve_ws_bytes(N, 1, Bv); its error block stays
+ * clear: one workgroup, no exchange) and the return codes as fs_mix_solve.  One persistent
+ * workgroup with p and buf in registers.  Requires 1 <= Bv <= 64 and N <= 4096, else
+ * FS_EUNSUPPORTED (there is no multi-CU form and no rank-blocked layout under MSE).
+ * ------------------------------------------------------------------------- */
+int fs_mix_solve_mse(const float* d_Z, const float* d_y, const int32_t* d_perms, int N, int n_val, int epochs,
+                     int Bv, float lr_p, float momentum, float* d_p, float* d_buf, int* d_first, void* d_ws,
+                     int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * (ABI 12) fs_mix_solve on the rank-blocked Z that one all-gather of the per-rank
@@ -469,6 +515,14 @@ typedef struct fs_plan_desc {
                                   local training, so they run beside what follows it (FedAMW: the
                                   p-solve, which leaves most CUs idle) instead of holding CUs a
                                   group of the split kernel is waiting for */
+  /* (ABI 17) the task's loss: 0 = cross-entropy (everything above), 1 = MSE at one output column
+     (tools.py:183-184, 223-224): TRAIN launches fs_local_train_mse on d_y, EVAL launches
+     fs_eval_mse on d_y_t; C and G must both be 1 (else FS_EINVAL); d_labels / d_labels_t are not
+     read.  FS_PHASE_EVAL_DEFER is accepted but never fused: fs_plan_eval_blocks is 0 and the
+     evaluation runs as a launch of its own in the call that would have carried it. */
+  int loss;
+  const float* d_y;            /* [rows] float targets (loss == 1) */
+  const float* d_y_t;          /* [n_t] float test targets (loss == 1) */
 } fs_plan_desc;
 
 int64_t fs_plan_desc_size(void);   /* sizeof(fs_plan_desc), for binding-layout checks */

@@ -33,17 +33,25 @@ _SIGS = {
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                  C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_local_train_mse': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fs_aggregate': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
+    'fs_eval_mse': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p]),
     'fs_mix_z': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p]),
     'fs_mix_solve_ws_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'fs_mix_solve': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_mix_solve_mse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p]),
     'fs_mix_solve_blocked': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int64, C.c_void_p]),
@@ -72,7 +80,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
@@ -109,6 +117,7 @@ class PlanDesc(C.Structure):
         ('d_phi_t', C.c_void_p), ('d_labels_t', C.c_void_p), ('n_t', C.c_int), ('d_eval_ws', C.c_void_p),
         ('d_eval_hist', C.c_void_p), ('shuffle_device', C.c_int), ('host_threads', C.c_int),
         ('shuffle_after_train', C.c_int),
+        ('loss', C.c_int), ('d_y', C.c_void_p), ('d_y_t', C.c_void_p),      # ABI 17: 0 = cross-entropy, 1 = MSE
     ]
 
 _lib = None
@@ -257,6 +266,8 @@ KERNEL_SOURCES = {
                     'eval_rows.h', 'lanes.h'),
     'mix_solve': ('mixture.hip', 'common.h', 'lanes.h'),
     'mix_z': ('mix_z.hip', 'common.h'),
+    'local_train_mse': ('local_train_mse.hip', 'mse_rows.h', 'common.h'),
+    'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),
 }
 
 

@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "finalize.h"
+#include "mse_rows.h"
 #include "mt_replay.h"
 
 namespace fs {
@@ -231,8 +232,12 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
   FS_REQUIRE(desc && out, "null pointer");
   const fs_plan_desc& d = *desc;
   FS_REQUIRE(d.N >= 1 && d.E >= 0 && d.C >= 1 && d.ld >= 64 && d.ld % 64 == 0, "bad sizes");
-  FS_REQUIRE(d.h_n && d.d_phi && d.d_row_off && d.d_labels && d.d_W_g && d.d_W_out && d.d_loss_hist,
+  FS_REQUIRE(d.loss == 0 || d.loss == 1, "loss must be 0 (cross-entropy) or 1 (MSE)");
+  FS_REQUIRE(d.h_n && d.d_phi && d.d_row_off && (d.loss ? (const void*)d.d_y : (const void*)d.d_labels) && d.d_W_g &&
+                 d.d_W_out && d.d_loss_hist,
              "null pointer");
+  // MSE (tools.py:183-184): one output column, one workgroup per client, no exchange workspace
+  FS_REQUIRE(d.loss == 0 || (d.C == 1 && d.G == 1), "the MSE plan needs C == 1 and G == 1");
   *out = nullptr;
   fs_plan* p = new fs_plan();
   p->d = d;
@@ -258,7 +263,8 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
   }
   // FS_PHASE_EVAL_DEFER: a parallel split launch that leaves CUs idle evaluates the previous
   // round's global model on them (fs_tuning.no_eval_fuse turns this off)
-  if (d.d_phi_t && d.n_t > 0 && d.d_labels_t && d.d_eval_ws && d.C <= 16 && d.G > 1 && !d.chained) {
+  // (the MSE plan never fuses: G == 1, fuse_E stays 0 and a deferred evaluation runs as a launch of its own)
+  if (d.loss == 0 && d.d_phi_t && d.n_t > 0 && d.d_labels_t && d.d_eval_ws && d.C <= 16 && d.G > 1 && !d.chained) {
     if (!fs::tuning().no_eval_fuse) {
       const int idle = fs::split_idle_cus(d.N, d.C, d.B, d.ld, d.G, 0);
       p->fuse_E = (int)std::min<int64_t>(idle, (d.n_t + 15) / 16);
@@ -512,13 +518,31 @@ static int run_shuffle_job(fs_plan* p, const int64_t* h_seeds, int t) {
   return FS_OK;
 }
 
+// round te's evaluation as a launch of its own, by the plan's loss
+static int plan_eval(const fs_plan_desc& d, int te, hipStream_t st) {
+  double* out = d.d_eval_hist + 2 * (int64_t)te;
+  if (d.loss) return fs::eval_mse(d.d_phi_t, d.ld, d.d_y_t, d.n_t, d.d_W_g, out, d.d_eval_ws, st);
+  return fs_eval(d.d_phi_t, d.ld, d.d_labels_t, d.n_t, d.d_W_g, d.C, out, d.d_eval_ws, st);
+}
+
+// round t's local training on the shuffles at `perms`, by the plan's loss
+static int plan_train(fs_plan* p, const int32_t* perms, int t, float lr, const fs::FuseEval* fuse, hipStream_t st) {
+  const fs_plan_desc& d = p->d;
+  double* loss = d.d_loss_hist + (int64_t)t * d.N;
+  if (d.loss)
+    return fs::local_train_mse(d.d_phi, d.ld, d.d_row_off, d.d_y, perms, d.d_order, d.N, d.B, d.E, lr, d.mu, d.prox,
+                               d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out, loss, st);
+  return fs::local_train(d.d_phi, d.ld, d.d_row_off, d.d_labels, perms, d.d_order, d.N, d.C, d.B, d.E, lr, d.mu, d.prox,
+                         d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out, loss, d.G, d.d_ws, d.ws_bytes, st,
+                         p->max_client_steps, fuse);
+}
+
 // the deferred evaluation of round p->eval_pending as a launch of its own
 static int flush_eval(fs_plan* p, hipStream_t st) {
   if (p->eval_pending < 0) return FS_OK;
-  const fs_plan_desc& d = p->d;
   const int te = p->eval_pending;
   p->eval_pending = -1;
-  return fs_eval(d.d_phi_t, d.ld, d.d_labels_t, d.n_t, d.d_W_g, d.C, d.d_eval_hist + 2 * (int64_t)te, d.d_eval_ws, st);
+  return plan_eval(p->d, te, st);
 }
 
 // ABI 15: complete every evaluation this plan still holds -- a deferred one
@@ -573,10 +597,7 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
       FS_HIP(hipStreamWaitEvent(st, p->uploaded[sc], 0), "fs_plan_round");
       p->slot_waited[sc] = c;
     }
-    const int rc = fs::local_train(d.d_phi, d.ld, d.d_row_off, d.d_labels, p->d_perm[sc] + (int64_t)r * p->perm_len,
-                                  d.d_order, d.N, d.C, d.B, d.E, lr, d.mu, d.prox, d.lam, d.reg, d.chained, d.d_W_g,
-                                  d.d_W_out, d.d_loss_hist + (int64_t)t * d.N, d.G, d.d_ws, d.ws_bytes, st,
-                                  p->max_client_steps, fused ? &fuse : nullptr);
+    const int rc = plan_train(p, p->d_perm[sc] + (int64_t)r * p->perm_len, t, lr, fused ? &fuse : nullptr, st);
     if (rc != FS_OK) return rc;
     if (r == p->slot_nrounds[sc] - 1) {            // the chunk's last round releases the slot
       FS_HIP(hipEventRecord(p->consumed[sc], st), "fs_plan_round");
@@ -595,10 +616,7 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
       if (p->slot_round[s] != t) return fail(FS_EINVAL, "fs_plan_round: shuffles of this round were not prepared");
     }
     FS_HIP(hipStreamWaitEvent(st, p->uploaded[s], 0), "fs_plan_round");
-    const int rc = fs::local_train(d.d_phi, d.ld, d.d_row_off, d.d_labels, p->d_perm[s], d.d_order, d.N, d.C, d.B,
-                                   d.E, lr, d.mu, d.prox, d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out,
-                                   d.d_loss_hist + (int64_t)t * d.N, d.G, d.d_ws, d.ws_bytes, st,
-                                   p->max_client_steps, fused ? &fuse : nullptr);
+    const int rc = plan_train(p, p->d_perm[s], t, lr, fused ? &fuse : nullptr, st);
     if (rc != FS_OK) return rc;
     FS_HIP(hipEventRecord(p->consumed[s], st), "fs_plan_round");
     p->cons_recorded[s] = true;
@@ -624,13 +642,13 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
   // (a finaliser still pending here is launched by the next fs_plan_round call -- any call that
   // trains or does not aggregate runs it first; results are read after such a call)
   if (phases & FS_PHASE_EVAL) {
-    FS_REQUIRE(d.d_phi_t && d.d_labels_t && d.d_eval_hist && d.d_eval_ws, "no test set");
-    if ((phases & FS_PHASE_EVAL_DEFER) && p->fuse_E > 0) {
-      p->eval_pending = t;                         // evaluated by the next TRAIN launch
-      return FS_OK;
+    FS_REQUIRE(d.d_phi_t && (d.loss ? (const void*)d.d_y_t : (const void*)d.d_labels_t) && d.d_eval_hist && d.d_eval_ws,
+               "no test set");
+    if ((phases & FS_PHASE_EVAL_DEFER) && (p->fuse_E > 0 || d.loss)) {
+      p->eval_pending = t;                         // evaluated by the next TRAIN launch (MSE: never fused,
+      return FS_OK;                                // a launch of its own in the call that would have carried it)
     }
-    const int rc = fs_eval(d.d_phi_t, d.ld, d.d_labels_t, d.n_t, d.d_W_g, d.C, d.d_eval_hist + 2 * (int64_t)t,
-                           d.d_eval_ws, stream);
+    const int rc = plan_eval(d, t, st);
     if (rc != FS_OK) return rc;
   }
   return FS_OK;

@@ -2,7 +2,7 @@
 
 HBM layout (one GPU; see DESIGN.md "Data layout"):
   phi      [rows, ld]   fp32  all local clients' features, CSR by client (row_off), D zero-padded to ld % 64 == 0
-  labels   [rows]       int32
+  labels   [rows]       int32  (loss='mse': y [rows] fp32 targets instead, the [n, 1] targets flattened)
   row_off  [N+1]        int64
   perms    [E*rows]     int32 this round's shuffles, client j epoch e at E*row_off[j] + e*n_j
   W_out    [N, C, ld]   fp32  the clients x params buffer (each client's trained weights)
@@ -33,9 +33,11 @@ def _to_device_f32(xs, device):
 
 
 class Features:
-    """Rows of features packed CSR-style in HBM (``phi[rows, ld]``) plus int32 labels."""
+    """Rows of features packed CSR-style in HBM (``phi[rows, ld]``) plus int32 labels --
+    or, with ``float_targets`` (the regression task), a float32 ``y[rows]`` buffer instead
+    (``labels`` is then None)."""
 
-    def __init__(self, X_list, y_list, D, device, ld=None):
+    def __init__(self, X_list, y_list, D, device, ld=None, float_targets=False):
         self.device = device
         self.D = int(D)
         self.ld = ld or pad_ld(D)
@@ -47,12 +49,17 @@ class Features:
             if X.dim() != 2 or X.shape[1] != self.D:
                 raise ValueError('feature matrix must be [n, D=%d], got %s' % (self.D, tuple(X.shape)))
         self.phi = torch.zeros(max(rows, 1), self.ld, device=device, dtype=torch.float32)
+        tdt = torch.float32 if float_targets else torch.int32
         if rows:
             self.phi[:rows, :self.D].copy_(_to_device_f32([torch.as_tensor(x) for x in X_list], device))
-            y = torch.cat([torch.as_tensor(v).reshape(-1).to('cpu', torch.int64) for v in y_list])
-            self.labels = y.to(torch.int32).to(device)
+            y = torch.cat([torch.as_tensor(v).reshape(-1).to('cpu', torch.float32 if float_targets else torch.int64)
+                           for v in y_list])
+            tgt = y.to(tdt).to(device)
         else:
-            self.labels = torch.zeros(1, dtype=torch.int32, device=device)
+            tgt = torch.zeros(1, dtype=tdt, device=device)
+        self.labels = None if float_targets else tgt
+        self.y = tgt if float_targets else None
+        self.targets = tgt
         self.row_off_dev = torch.from_numpy(self.row_off).to(device)
 
 
@@ -149,9 +156,19 @@ class LocalTrainer:
     mode as persistent groups over the clients -- two clients per group in the pair form
     (G | _lib.G_PAIR) where the shape allows it -- in chained mode as one group walking the
     chain); 1 forces one workgroup per client, G a split width, G | _lib.G_PAIR the pair form,
-    G | _lib.G_TEAMS the team form, G | _lib.G_PIPE the pipelined split form."""
+    G | _lib.G_TEAMS the team form, G | _lib.G_PIPE the pipelined split form.
 
-    def __init__(self, feats, C, B, E, split=None, chained=False, rows=None, prox=False):
+    ``loss='mse'`` (the regression task: C = 1, float targets in ``feats``): fs_local_train_mse,
+    one workgroup per client, no planner call and no workspace."""
+
+    def __init__(self, feats, C, B, E, split=None, chained=False, rows=None, prox=False, loss='ce'):
+        if loss not in ('ce', 'mse'):
+            raise ValueError("loss must be 'ce' or 'mse'")
+        self.task = loss                  # ('loss' is the trainer's loss buffer below)
+        if loss == 'mse' and (int(C) != 1 or feats.y is None):
+            raise ValueError("loss='mse' needs C == 1 and Features(float_targets=True)")
+        if loss == 'ce' and feats.labels is None:
+            raise ValueError("loss='ce' needs integer labels")
         self.f = feats
         self.C, self.B, self.E = int(C), int(B), int(E)
         dev = feats.device
@@ -170,6 +187,11 @@ class LocalTrainer:
         steps = self.E * ((ns + self.B - 1) // self.B)
         order = np.argsort(-steps, kind='stable').astype(np.int32)     # LPT: longest clients dispatched first
         self.order = torch.from_numpy(order).to(dev)
+        if loss == 'mse':
+            if split not in (None, 1):
+                raise _lib.FedsimError('fs_local_train_mse has no split form (one workgroup per client)')
+            self.G, self.pair, self.teams, self.pipe, self.width, self.ws = 1, False, False, False, 1, None
+            return
         import ctypes
         g, wsb = ctypes.c_int(0 if split is None else int(split)), ctypes.c_int64(0)
         max_en = int(self.E * ns.max()) if N else 0
@@ -222,6 +244,15 @@ class LocalTrainer:
         L = _lib.lib()
         loss = self.loss if loss_out is None else loss_out
         perms = self.shuffler.acquire(slot)
+        if self.task == 'mse':
+            _lib.check(L.fs_local_train_mse(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), _lib.ptr(f.y),
+                                            _lib.ptr(perms), None if chained else _lib.ptr(self.order),
+                                            self.N, self.B, self.E, float(lr), float(mu), int(bool(prox)),
+                                            float(lam), int(bool(reg)), int(bool(chained)), _lib.ptr(W_start),
+                                            _lib.ptr(self.W_out), _lib.ptr(loss), _lib.stream_ptr()),
+                       'fs_local_train_mse')
+            self.shuffler.release(slot)
+            return self.W_out, loss
         _lib.check(L.fs_local_train(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), _lib.ptr(f.labels),
                                     _lib.ptr(perms), None if chained else _lib.ptr(self.order),
                                     self.N, self.C, self.B, self.E, float(lr), float(mu), int(bool(prox)),
@@ -248,7 +279,13 @@ class RoundPlan:
         self._keep = [trainer, W_g, loss_hist, p, aggregator, evaluator, eval_hist]
         self._h_n = np.ascontiguousarray(f.ns, dtype=np.int64)
         d = _lib.PlanDesc()
-        d.d_phi, d.ld, d.d_row_off, d.d_labels = f.phi.data_ptr(), f.ld, f.row_off_dev.data_ptr(), f.labels.data_ptr()
+        d.d_phi, d.ld, d.d_row_off = f.phi.data_ptr(), f.ld, f.row_off_dev.data_ptr()
+        self.loss = trainer.task
+        d.loss = 1 if self.loss == 'mse' else 0
+        if self.loss == 'mse':
+            d.d_y = f.y.data_ptr()
+        else:
+            d.d_labels = f.labels.data_ptr()
         d.d_order = None if chained else trainer.order.data_ptr()
         d.h_n = self._h_n.ctypes.data
         d.N, d.C, d.B, d.E, d.G = trainer.N, trainer.C, trainer.B, trainer.E, trainer.G
@@ -262,7 +299,13 @@ class RoundPlan:
             d.d_agg_ws, d.agg_ws_floats, d.agg_chunks = aggregator.ws.data_ptr(), aggregator.ws.numel(), \
                 int(aggregator.chunks)
         if evaluator is not None:
-            d.d_phi_t, d.d_labels_t, d.n_t = evaluator.f.phi.data_ptr(), evaluator.f.labels.data_ptr(), evaluator.n
+            if evaluator.loss != self.loss:
+                raise ValueError('RoundPlan: the evaluator and the trainer disagree on the loss')
+            d.d_phi_t, d.n_t = evaluator.f.phi.data_ptr(), evaluator.n
+            if self.loss == 'mse':
+                d.d_y_t = evaluator.f.y.data_ptr()
+            else:
+                d.d_labels_t = evaluator.f.labels.data_ptr()
             d.d_eval_ws, d.d_eval_hist = evaluator.ws.data_ptr(), eval_hist.data_ptr()
         d.shuffle_device = int(bool(shuffle_device))
         d.host_threads = int(host_threads)
@@ -328,10 +371,16 @@ class Aggregator:
 
 
 class Evaluator:
-    """fs_eval on a resident test set."""
+    """fs_eval on a resident test set (``loss='mse'``: fs_eval_mse on float targets, C = 1)."""
 
-    def __init__(self, X_test, y_test, D, C, device, ld=None):
-        self.f = Features([torch.as_tensor(X_test)], [torch.as_tensor(y_test)], D, device, ld)
+    def __init__(self, X_test, y_test, D, C, device, ld=None, loss='ce'):
+        if loss not in ('ce', 'mse'):
+            raise ValueError("loss must be 'ce' or 'mse'")
+        if loss == 'mse' and int(C) != 1:
+            raise ValueError("loss='mse' needs C == 1")
+        self.loss = loss
+        self.f = Features([torch.as_tensor(X_test)], [torch.as_tensor(y_test)], D, device, ld,
+                          float_targets=loss == 'mse')
         self.C = int(C)
         self.n = int(self.f.rows)
         if self.n < 1:
@@ -339,16 +388,28 @@ class Evaluator:
         self.ws = torch.empty(int(_lib.lib().fs_eval_ws_doubles(self.n)), dtype=torch.float64, device=device)
 
     def run(self, W, out2):
+        if self.loss == 'mse':
+            _lib.check(_lib.lib().fs_eval_mse(_lib.ptr(self.f.phi), self.f.ld, _lib.ptr(self.f.y), self.n, _lib.ptr(W),
+                                              _lib.ptr(out2), _lib.ptr(self.ws), _lib.stream_ptr()), 'fs_eval_mse')
+            return out2
         _lib.check(_lib.lib().fs_eval(_lib.ptr(self.f.phi), self.f.ld, _lib.ptr(self.f.labels), self.n, _lib.ptr(W),
                                       self.C, _lib.ptr(out2), _lib.ptr(self.ws), _lib.stream_ptr()), 'fs_eval')
         return out2
 
 
 class Mixture:
-    """FedAMW's mixture-weight estimation: Z GEMM + persistent p-SGD (tools.py:435-453)."""
+    """FedAMW's mixture-weight estimation: Z GEMM + persistent p-SGD (tools.py:435-453).
+    ``loss='mse'``: float validation targets, C = 1, fs_mix_solve_mse (one workgroup; the
+    rank-blocked Z layout is never asked for)."""
 
-    def __init__(self, X_val, y_val, D, C, N, Bv, p0, device, ld=None, momentum=0.9):
-        self.f = Features([torch.as_tensor(X_val)], [torch.as_tensor(y_val)], D, device, ld)
+    def __init__(self, X_val, y_val, D, C, N, Bv, p0, device, ld=None, momentum=0.9, loss='ce'):
+        if loss not in ('ce', 'mse'):
+            raise ValueError("loss must be 'ce' or 'mse'")
+        if loss == 'mse' and int(C) != 1:
+            raise ValueError("loss='mse' needs C == 1")
+        self.loss = loss
+        self.f = Features([torch.as_tensor(X_val)], [torch.as_tensor(y_val)], D, device, ld,
+                          float_targets=loss == 'mse')
         self.C, self.N, self.Bv = int(C), int(N), int(Bv)
         self.nv = int(self.f.rows)
         if self.nv < 1:
@@ -365,7 +426,10 @@ class Mixture:
         self.blocks = 1          # > 1: Z holds `blocks` rank blocks [blocks][n_val][C][N/blocks] (dist.py)
 
     def blocked_covers(self, epochs):
-        """Whether fs_mix_solve_blocked reads this shape (the qmc solver; include/fedsim.h)."""
+        """Whether fs_mix_solve_blocked reads this shape (the qmc solver; include/fedsim.h).
+        Never under loss='mse'."""
+        if self.loss == 'mse':
+            return False
         return bool(_lib.lib().fs_mix_solve_blocked_covers(self.N, self.C, self.nv, int(epochs), self.Bv))
 
     def check_errors(self):
@@ -407,6 +471,13 @@ class Mixture:
             self.prepare(seeds, slot)
         epochs = self.shuffler.P
         perms = self.shuffler.acquire(slot)
+        if self.loss == 'mse':
+            _lib.check(L.fs_mix_solve_mse(_lib.ptr(self.Z), _lib.ptr(self.f.y), _lib.ptr(perms), self.N, self.nv, epochs,
+                                          self.Bv, float(lr_p), self.momentum, _lib.ptr(self.p), _lib.ptr(self.buf),
+                                          _lib.ptr(self.first), _lib.ptr(self.ws), self.ws.numel(),
+                                          _lib.stream_ptr()), 'fs_mix_solve_mse')
+            self.shuffler.release(slot)
+            return self.p
         tail = (_lib.ptr(self.f.labels), _lib.ptr(perms), self.N, self.C, self.nv, epochs, self.Bv, float(lr_p),
                 self.momentum, _lib.ptr(self.p), _lib.ptr(self.buf), _lib.ptr(self.first), _lib.ptr(self.ws),
                 self.ws.numel(), _lib.stream_ptr())

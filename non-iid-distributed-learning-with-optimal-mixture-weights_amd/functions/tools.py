@@ -8,7 +8,8 @@ Same names, positional signatures, defaults and return values as the reference
                                              mu, lambda_reg_if, lambda_reg, round)
 
 * ``X_train`` / ``y_train``: per-client lists of feature matrices [n_j, D] (fp32) and
-  integer labels, on CPU or GPU; ``X_test`` / ``y_test`` likewise; FedAMW takes the
+  integer labels (``type='regression'``: float targets of shape [n_j, 1]), on CPU or GPU;
+  ``X_test`` / ``y_test`` likewise; FedAMW takes the
   reference's ``validloader`` (a DataLoader over a TensorDataset, batch 16, shuffle).
 * Returns three CPU float32 tensors of length ``round``; ``test_acc`` is in percent.
   One ``Test loss: ..., \\t Test Acc: ...`` line per round is printed (tools.py:236),
@@ -27,8 +28,17 @@ Keyword-only extensions (not in the reference):
   ``stats={'trace': True}``, the global model after every round in ``'W_rounds'``).
 
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
-CPU path.  ``type`` must be 'classification' (the reference's MSE branch,
-tools.py:183-184, is not on the benchmarked path).
+CPU path.
+
+``type='classification'`` selects cross-entropy, ``type='regression'`` the reference's
+``nn.MSELoss(reduction='mean')`` branch (tools.py:181-184, 221-224, 297-300, 419-422) at
+``num_classes = 1`` (the reference's regression loader, utils.py:121, 167) with float targets
+of shape [n, 1] (utils.py:81-82): fs_local_train_mse / fs_eval_mse / fs_mix_solve_mse.
+``test_acc`` is then the reference's degenerate value, 100 * #{y_test == 0} / n
+(comp_accuracy's top-1 index of a one-column output is always 0).  1-D float targets -- which
+the reference broadcasts into a [B, B] loss -- are rejected with a ValueError, as are integer
+or non-finite targets; ``num_classes != 1`` raises NotImplementedError, any other ``type`` a
+ValueError.  ``stats['W_global']`` is [1, D] and ``stats['W_rounds']`` [R, 1, D].
 """
 
 import numpy as np
@@ -76,11 +86,34 @@ def _check_labels(ys, num_classes, what):
                                                                               int(y.max())))
 
 
+def _check_targets(ys, what):
+    """Regression targets: float [n, 1], finite.  The reference's MSELoss broadcasts a [B, 1]
+    output against 1-D [B] targets into a [B, B] loss (torch warns; every row then regresses
+    onto the batch mean) -- not reproduced."""
+    for y in ys:
+        y = torch.as_tensor(y)
+        if not y.dtype.is_floating_point:
+            raise ValueError("%s targets must be floating point for type='regression', got %s" % (what, y.dtype))
+        if y.dim() == 1:
+            raise ValueError("%s targets are 1-D: the reference's MSELoss would broadcast its [B, 1] output against "
+                             "[B] targets into a [B, B] loss; pass y.reshape(-1, 1)" % what)
+        if y.dim() != 2 or y.shape[1] != 1:
+            raise ValueError('%s targets must have shape [n, 1], got %s' % (what, tuple(y.shape)))
+        if y.numel() and not bool(torch.isfinite(y).all()):
+            raise ValueError('%s targets must be finite' % what)
+
+
+def _loss_of(type):
+    return 'mse' if type == 'regression' else 'ce'
+
+
 def _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round, y_test=None, y_val=None,
                   train_labels=True):
-    if type != 'classification':
-        raise NotImplementedError("only type='classification' is implemented (tools.py:181-184 MSE branch "
-                                  "is out of scope)")
+    if type not in ('classification', 'regression'):
+        raise ValueError("type must be 'classification' or 'regression', got %r" % (type,))
+    if type == 'regression' and int(num_classes) != 1:
+        raise NotImplementedError("type='regression' is implemented for num_classes == 1 (the reference's "
+                                  "regression loader, utils.py:121, 167); multi-output regression is out of scope")
     if len(X_train) != len(y_train) or len(y_train) == 0:
         raise ValueError('X_train and y_train must be equal-length non-empty lists')
     for y in y_train:
@@ -93,6 +126,14 @@ def _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round,
         raise NotImplementedError('batch_size must be in [1, 64]')
     if epoch < 1 or round < 0:
         raise ValueError('epoch must be >= 1 and round >= 0')
+    if type == 'regression':
+        # (every client's targets, whatever train_labels says: shapes are checked before any device is touched)
+        _check_targets(y_train, 'training')
+        if y_test is not None:
+            _check_targets([y_test], 'test')
+        if y_val is not None:
+            _check_targets([y_val], 'validation')
+        return
     if train_labels:
         _check_labels(y_train, num_classes, 'training')
     if y_test is not None:
@@ -150,7 +191,9 @@ class Federation:
         self.shards = dist.shard_lpt(dist.client_work(ns, E, B), nranks) if self.sharded else [np.arange(N)]
         self.mine = self.shards[self.rank] if self.sharded else self.shards[0]
         mine = self.mine
-        _check_labels([y_train[j] for j in mine], num_classes, 'training')
+        loss = self.loss = _loss_of(type)
+        if loss == 'ce':
+            _check_labels([y_train[j] for j in mine], num_classes, 'training')
         dev = _device()
 
         # model init + mixture weights exactly as the reference (tools.py:330-333, 414-417)
@@ -158,7 +201,8 @@ class Federation:
         self.p_all = torch.tensor(ns / sum(ns), dtype=torch.float32)
 
         self.feats = engine.Features([torch.as_tensor(X_train[j]) for j in mine],
-                                     [torch.as_tensor(y_train[j]) for j in mine], D, dev)
+                                     [torch.as_tensor(y_train[j]) for j in mine], D, dev,
+                                     float_targets=loss == 'mse')
         ld = self.ld = self.feats.ld
         # sharded FedAMW: the p-solve's client axis is rank-major blocks of L columns (dist.py)
         self.zshard = algo == 'fedamw' and self.sharded
@@ -166,8 +210,8 @@ class Federation:
             self.L, self.pos = dist.solver_layout(self.shards)
             self.pos_dev = torch.from_numpy(self.pos).to(dev)
         self.trainer = engine.LocalTrainer(self.feats, C, B, E, chained=self.chained,
-                                           rows=self.L if self.zshard else None, prox=prox)
-        self.evaluator = engine.Evaluator(X_test, y_test, D, C, dev, ld)
+                                           rows=self.L if self.zshard else None, prox=prox, loss=loss)
+        self.evaluator = engine.Evaluator(X_test, y_test, D, C, dev, ld, loss=loss)
         self.W_g = torch.zeros(C, ld, device=dev, dtype=torch.float32)
         self.W_g[:, :D].copy_(W_init)
         p_dev = self.p_all.to(dev)
@@ -184,7 +228,7 @@ class Federation:
                 Ns = nranks * self.L
                 p0 = torch.zeros(Ns, dtype=torch.float32)
                 p0[torch.from_numpy(self.pos)] = self.p_all
-                self.mixture = engine.Mixture(Xv, yv, D, C, Ns, Bv, p0, dev, ld)
+                self.mixture = engine.Mixture(Xv, yv, D, C, Ns, Bv, p0, dev, ld, loss=loss)
                 # the qmc solver reads the all-gathered rank blocks as they land (no layout copy);
                 # which layout to gather is decided again every round, right before the
                 # all-gather (round()), under the tuning the enqueueing thread has then
@@ -194,7 +238,7 @@ class Federation:
                 self.p_slice = lambda p: p[lo:lo + len(mine)]
                 self.agg = engine.Aggregator(len(mine), C, ld, dev)
             else:
-                self.mixture = engine.Mixture(Xv, yv, D, C, N, Bv, self.p_all, dev, ld)
+                self.mixture = engine.Mixture(Xv, yv, D, C, N, Bv, self.p_all, dev, ld, loss=loss)
                 self.agg = engine.Aggregator(N, C, ld, dev)
             self.p_hist = torch.empty(R, N, dtype=torch.float32, device=dev)
         else:
@@ -436,13 +480,14 @@ def feature_mapping(X_train, X_test, k_par=10, D=200, type='gaussian'):
 # --------------------------------------------------------------------------- #
 # Single-shot algorithms (tools.py:240-326)
 # --------------------------------------------------------------------------- #
-def _chain_train(X_train, y_train, W_init, D, C, lr, epoch, batch_size, prox, mu, reg, lam, dev):
+def _chain_train(X_train, y_train, W_init, D, C, lr, epoch, batch_size, prox, mu, reg, lam, dev, loss='ce'):
     """One shared model trained by the clients in turn (tools.py:263-266 / 284-287: train_loop
     mutates the one ``model``), each for ``epoch`` epochs and anchored (prox) to its start --
     one fs_local_train launch in chained mode.  Consumes the generator like the reference
     (epoch passes per client, client-major).  Returns (feats, W_out [N, C, ld], loss [N])."""
-    feats = engine.Features([torch.as_tensor(x) for x in X_train], [torch.as_tensor(y) for y in y_train], D, dev)
-    trainer = engine.LocalTrainer(feats, C, batch_size, epoch, chained=True, prox=prox)
+    feats = engine.Features([torch.as_tensor(x) for x in X_train], [torch.as_tensor(y) for y in y_train], D, dev,
+                            float_targets=loss == 'mse')
+    trainer = engine.LocalTrainer(feats, C, batch_size, epoch, chained=True, prox=prox, loss=loss)
     trainer.upload_perms(rng.draw_pass_seeds(trainer.N * epoch))
     W0 = torch.zeros(C, feats.ld, device=dev, dtype=torch.float32)
     W0[:, :D].copy_(W_init)
@@ -472,10 +517,12 @@ def Centralized(X_train, y_train, X_test, y_test, type='classification', num_cla
     C = int(num_classes)
     W_init = init_weights(D, C)
     Xc = torch.cat([torch.as_tensor(x).to(dev, torch.float32) for x in X_train], 0)
-    yc = torch.cat([torch.as_tensor(y).reshape(-1).to('cpu', torch.int64) for y in y_train], 0)
+    task = _loss_of(type)
+    yc = torch.cat([torch.as_tensor(y).reshape(-1).to('cpu', torch.float32 if task == 'mse' else torch.int64)
+                    for y in y_train], 0)
     feats, trainer, W_out, loss = _chain_train([Xc], [yc], W_init, D, C, lr, epoch, batch_size, prox, mu,
-                                               lambda_reg_if, lambda_reg, dev)
-    ev = engine.Evaluator(X_test, y_test, D, C, dev, feats.ld)
+                                               lambda_reg_if, lambda_reg, dev, loss=task)
+    ev = engine.Evaluator(X_test, y_test, D, C, dev, feats.ld, loss=task)
     out2 = torch.empty(2, dtype=torch.float64, device=dev)
     _test(ev, W_out[0], out2)
     trainer.check_errors()
@@ -498,13 +545,14 @@ def Distributed(X_train, y_train, X_test, y_test, type='classification', num_cla
     W_init = init_weights(D, C)
     ns = np.array([len(y) for y in y_train])
     p = torch.tensor(ns / sum(ns), dtype=torch.float32)
+    task = _loss_of(type)
     feats, trainer, W_out, loss = _chain_train(X_train, y_train, W_init, D, C, lr, epoch, batch_size, prox, mu,
-                                               lambda_reg_if, lambda_reg, dev)
+                                               lambda_reg_if, lambda_reg, dev, loss=task)
     ld = feats.ld
     agg = engine.Aggregator(len(ns), C, ld, dev, chunks=1)
     W_g = torch.empty(C, ld, device=dev, dtype=torch.float32)
     agg.run(W_out, p.to(dev), W_g)
-    ev = engine.Evaluator(X_test, y_test, D, C, dev, ld)
+    ev = engine.Evaluator(X_test, y_test, D, C, dev, ld, loss=task)
     out2 = torch.empty(2, dtype=torch.float64, device=dev)
     _test(ev, W_g, out2)
     trainer.check_errors()
@@ -539,14 +587,15 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
     ns = np.array([len(y) for y in y_train])
     N = len(ns)
     p0 = torch.tensor(ns / np.sum(ns), dtype=torch.float32)
+    task = _loss_of(type)
     feats, trainer, W_out, loss = _chain_train(X_train, y_train, W_init, D, C, lr, epoch, batch_size, prox, mu,
-                                               lambda_reg_if, lambda_reg, dev)
+                                               lambda_reg_if, lambda_reg, dev, loss=task)
     ld = feats.ld
     Xv, yv = validloader.dataset.tensors[:2]
     if not isinstance(validloader.sampler, torch.utils.data.RandomSampler):
         raise NotImplementedError('validloader must shuffle (exp.py:99)')
-    mix = engine.Mixture(Xv, yv, D, C, N, int(validloader.batch_size), p0, dev, ld, momentum=0.0)
-    ev = engine.Evaluator(X_test, y_test, D, C, dev, ld)
+    mix = engine.Mixture(Xv, yv, D, C, N, int(validloader.batch_size), p0, dev, ld, momentum=0.0, loss=task)
+    ev = engine.Evaluator(X_test, y_test, D, C, dev, ld, loss=task)
     agg1 = engine.Aggregator(1, C, ld, dev, chunks=1)
     aggN = engine.Aggregator(N, C, ld, dev, chunks=1)
     W_agg = W_out.clone()                       # row 0 rewritten every round, rows 1.. = W_j
