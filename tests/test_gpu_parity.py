@@ -504,14 +504,15 @@ def test_aggregate_bitexact_and_chunked(amd):
     assert np.abs(out.cpu().numpy() - ref).max() <= 1e-6 * np.abs(ref).max()
 
 
-@pytest.mark.parametrize('N', [1, 9, 15, 16, 37, 100, 300, 512, 513, 1250])
+@pytest.mark.parametrize('N', [1, 9, 15, 16, 17, 37, 47, 48, 95, 96, 97, 100, 300, 512, 513, 1250])
 def test_aggregate_auto_forms(amd, N):
     """fs_aggregate with the shape's own choice (chunks = 0): one launch with in-workgroup
     sub-range folds for 16 <= N <= 512 (round 5), the two-launch chunked fold above, and the
     reference's exact single fold below 16 clients -- bitwise there; elsewhere only the order of
     the N products' fp32 sum differs, so each element lies within the classical bound of two
     recursive summations of the same terms, 2 (N - 1) u sum_j |p_j W_j| (u = 2^-24), of the
-    reference's fold."""
+    reference's fold.  17 / 47 / 48 / 95 / 96 / 97 are the steps of one_launch_sub (2, 4, 8 and
+    16 sub-ranges per position; 48 to 95 clients are the only ones on aggregate_one_kernel<8>)."""
     rs = np.random.RandomState(N)
     C, D = 10, 2048
     Ws = rs.normal(size=(N, C, D)).astype(np.float32)
@@ -528,6 +529,89 @@ def test_aggregate_auto_forms(amd, N):
         S = np.abs(p.astype(np.float64)[:, None, None] * Ws).sum(0)
         bound = 2.0 * (N - 1) * 2.0 ** -24 * S
         assert (np.abs(got.astype(np.float64) - ref) <= bound).all(), np.max(np.abs(got - ref) / bound)
+
+
+AGG_SENTINEL = 7.5
+
+
+def _aggregate_abi(amd, Ws, p, length, stride, chunks, ws_floats, out_extra=64):
+    """fs_aggregate through the C ABI on a clients x params buffer of row stride ``stride`` (the
+    gaps NaN), into an output buffer ``out_extra`` floats longer than ``length`` and with a
+    workspace of ``ws_floats`` floats (None: no workspace) followed by 64 more; the floats
+    behind the output and behind the workspace hold a sentinel that must survive.  Returns the
+    ``length`` results."""
+    dev = torch.device('cuda')
+    N = len(Ws)
+    Wb = torch.full((N, stride), float('nan'), device=dev)
+    Wb[:, :length] = torch.from_numpy(np.ascontiguousarray(Ws))
+    out = torch.full((length + out_extra,), AGG_SENTINEL, device=dev)
+    ws = None if ws_floats is None else torch.full((ws_floats + 64,), AGG_SENTINEL, device=dev)
+    L = amd.lib
+    L.check(L.lib().fs_aggregate(L.ptr(Wb), stride, L.ptr(torch.from_numpy(p).to(dev)), N, length, L.ptr(out),
+                                 L.ptr(ws), 0 if ws is None else ws_floats, chunks, L.stream_ptr()), 'fs_aggregate')
+    got = out.cpu().numpy()
+    assert (got[length:] == AGG_SENTINEL).all(), 'fs_aggregate wrote behind its output'
+    if ws is not None:
+        assert (ws[ws_floats:].cpu().numpy() == AGG_SENTINEL).all(), 'fs_aggregate wrote behind its workspace'
+    return got[:length]
+
+
+@pytest.mark.parametrize('length', [4, 64, 4 * 33, 4 * 257])
+@pytest.mark.parametrize('N', [9, 48, 600])
+def test_aggregate_geometry(amd, N, length):
+    """fs_aggregate off the one geometry the round uses: a parameter vector shorter than one
+    workgroup's positions (one float4, 16 of them), ragged against them (33: the <8> instance
+    owns 32 positions per workgroup) and against 256 (257), rows ``length + 64`` apart with NaN
+    in the gaps, an output buffer that goes on behind the result.  N = 9 is the exact single fold
+    (bitwise), 48 the one-launch form's <8> instance, 600 the two-launch chunked fold (8 chunks);
+    the bound of test_aggregate_auto_forms; no NaN picked up, nothing written past the end."""
+    rs = np.random.RandomState(N + length)
+    Ws = rs.normal(size=(N, length)).astype(np.float32)
+    p = rs.dirichlet(np.ones(N)).astype(np.float32)
+    ref = O.aggregate(list(Ws), p)
+    got = _aggregate_abi(amd, Ws, p, length, length + 64, 0, min(64, N) * length)
+    assert not np.isnan(got).any()
+    if N < 16:
+        np.testing.assert_array_equal(got, ref)
+        print('N = %d, len = %d: bitwise' % (N, length))
+    else:
+        S = np.abs(p.astype(np.float64)[:, None] * Ws).sum(0)
+        bound = 2.0 * (N - 1) * 2.0 ** -24 * S
+        frac = np.max(np.abs(got.astype(np.float64) - ref) / bound)
+        print('N = %d, len = %d: worst |W - ref| / bound = %.3f' % (N, length, frac))
+        assert frac <= 1.0
+
+
+def _chunked_fold(Ws, p, chunks):
+    """include/fedsim.h's order in numpy float32: consecutive ranges of ceil(N / chunks) clients,
+    each left-folded, then the partials folded in order."""
+    N = len(Ws)
+    per = -(-N // chunks)
+    parts = [O.aggregate(list(Ws[j:j + per]), p[j:j + per]) for j in range(0, N, per)]
+    acc = parts[0]
+    for q in parts[1:]:
+        acc = (acc + q).astype(np.float32)
+    return acc
+
+
+@pytest.mark.parametrize('N', [9, 37, 1250])
+def test_aggregate_chunked_fold_order(amd, N):
+    """Explicit chunks in {2, 3, 8}: bitwise the documented order (with up to 8 partials
+    fold_partials_kernel's tree is the plain in-order fold), on a length ragged against both
+    kernels' workgroups.  chunks = 8 with a workspace of 2 len floats is clamped to what the
+    workspace holds -- the two-chunk fold -- and without a workspace to the single fold."""
+    rs = np.random.RandomState(N)
+    length = 4 * 513
+    Ws = rs.normal(size=(N, length)).astype(np.float32)
+    p = rs.dirichlet(np.ones(N)).astype(np.float32)
+    for chunks in (2, 3, 8):
+        got = _aggregate_abi(amd, Ws, p, length, length, chunks, chunks * length)
+        np.testing.assert_array_equal(got, _chunked_fold(Ws, p, chunks), err_msg='chunks = %d' % chunks)
+    got = _aggregate_abi(amd, Ws, p, length, length, 8, 2 * length)
+    np.testing.assert_array_equal(got, _chunked_fold(Ws, p, 2), err_msg='workspace for two partials')
+    got = _aggregate_abi(amd, Ws, p, length, length, 8, None)
+    np.testing.assert_array_equal(got, O.aggregate(list(Ws), p), err_msg='no workspace')
+    print('N = %d: chunks 2, 3, 8 and the two clamps bitwise' % N)
 
 
 def test_eval_unit_golden(amd):
