@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 17
+#define FS_ABI_VERSION 18
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -311,6 +311,41 @@ int fs_eval(const float* d_phi, int64_t ld, const int32_t* d_labels, int n, cons
  * ------------------------------------------------------------------------- */
 int fs_eval_mse(const float* d_phi, int64_t ld, const float* d_y, int n, const float* d_W, double* d_out,
                 double* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 18) Per-client evaluation: the test_loop metrics (tools.py:218-237) of EVERY client
+ * model -- the reference's local_weights[j] (tools.py:340-343, 367-370, 430-433), which it
+ * never scores -- from their logits on a row set: d_Z in fs_mix_z's layout below, row v = C
+ * segments of ldN = (N + 3) & ~3 floats, client j at d_Z[v][c*ldN + j]; the padding columns
+ * N..ldN-1 are read and ignored (they may hold anything).  For every client j < N
+ *   d_out[2j]   = mean over the n rows of the cross-entropy of (Z[v][0*ldN+j], ...,
+ *                 Z[v][(C-1)*ldN+j]) against d_labels[v]
+ *   d_out[2j+1] = 100 * correct / n, top-1, ties to the lowest class index
+ * -- fs_eval's definitions.  Z is streamed once (16-byte loads along the client axis, the C
+ * logits of a client in registers); per-row losses are summed in fp64 per client over row
+ * blocks of fs_z_eval_block_rows() rows with fixed boundaries in absolute row numbers, one
+ * partial pair per (row block, client) in the caller-owned workspace d_ws
+ * ([row blocks][ldN][2] doubles: fs_z_eval_ws_doubles(n, N)); fs_z_eval_finish folds the row
+ * blocks per client in a fixed order.  No atomics, no cross-workgroup wait.  Two contracts:
+ *   column independence  a client's two numbers depend on its own column of Z and the labels
+ *                        alone -- not on N, its position or its neighbours (bitwise)
+ *   chunk independence   the rows may be added in chunks (a bounded scratch Z): the result is
+ *                        bitwise the same whatever the chunking
+ * fs_z_eval_add adds the partials of rows [row0, row0 + rows) of the n-row set: d_Z points at
+ * row row0 (the chunk's first row), d_labels at row 0; row0 must be a multiple of the row
+ * block, and only the set's last chunk may end inside a row block.  Every row must be added
+ * exactly once before fs_z_eval_finish (which serves both losses).  1 <= C <= 32.
+ * fs_z_eval_add_mse: nn.MSELoss at one output column (C = 1, d_Z [n][ldN], d_y [n] float):
+ * d_out[2j] = mean (Z[v][j] - y[v])^2, d_out[2j+1] = 100 * #{y == 0} / n -- fs_eval_mse's
+ * degenerate accuracy, the same for every client.
+ * ------------------------------------------------------------------------- */
+int fs_z_eval_block_rows(void);
+int64_t fs_z_eval_ws_doubles(int n, int N);
+int fs_z_eval_add(const float* d_Z, const int32_t* d_labels, int n, int row0, int rows, int N, int C,
+                  double* d_ws, int64_t ws_doubles, void* stream);
+int fs_z_eval_add_mse(const float* d_Z, const float* d_y, int n, int row0, int rows, int N, double* d_ws,
+                      int64_t ws_doubles, void* stream);
+int fs_z_eval_finish(const double* d_ws, int64_t ws_doubles, int n, int N, double* d_out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * FedAMW mixture step 1: Z[v][c*ldN + n] = sum_d X_val[v][d] * W_n[c][d], where

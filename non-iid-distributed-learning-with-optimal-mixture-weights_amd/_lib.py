@@ -43,6 +43,13 @@ _SIGS = {
                           C.c_void_p, C.c_void_p]),
     'fs_eval_mse': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
+    'fs_z_eval_block_rows': (C.c_int, []),
+    'fs_z_eval_ws_doubles': (C.c_int64, [C.c_int, C.c_int]),
+    'fs_z_eval_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                C.c_int64, C.c_void_p]),
+    'fs_z_eval_add_mse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_int64, C.c_void_p]),
+    'fs_z_eval_finish': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'fs_mix_z': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p]),
     'fs_mix_solve_ws_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
@@ -80,7 +87,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
@@ -268,6 +275,7 @@ KERNEL_SOURCES = {
     'mix_z': ('mix_z.hip', 'common.h'),
     'local_train_mse': ('local_train_mse.hip', 'mse_rows.h', 'common.h'),
     'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),
+    'z_eval': ('z_eval.hip', 'common.h'),
 }
 
 

@@ -397,6 +397,90 @@ class Evaluator:
         return out2
 
 
+class ClientEvaluator:
+    """Per-client evaluation (fs_z_eval_*): the (loss, accuracy %) of each of up to ``N`` client
+    models on a resident row set, as one fs_mix_z GEMM per row chunk and one streaming reduction
+    of its logits -- instead of N fs_eval calls that each read the features again.
+
+    ``feats``: a ``Features`` with one row set, shared with its owner (an ``Evaluator``'s or a
+    ``Mixture``'s ``.f``); labels, or float targets under ``loss='mse'`` (C = 1).  Owns the
+    partial-sum workspace and a scratch Z for ``run``, allocated at its first call and bounded by
+    ``scratch_bytes`` (``chunk_rows`` overrides the rows per chunk; rounded up to the row block).
+    A client's result depends on its own model and the rows alone -- not on ``n_models``, its
+    position or the chunking (bitwise; include/fedsim.h)."""
+
+    def __init__(self, feats, C, N, loss='ce', scratch_bytes=256 << 20, chunk_rows=None):
+        if loss not in ('ce', 'mse'):
+            raise ValueError("loss must be 'ce' or 'mse'")
+        if loss == 'mse' and (int(C) != 1 or feats.y is None):
+            raise ValueError("loss='mse' needs C == 1 and Features(float_targets=True)")
+        if loss == 'ce' and feats.labels is None:
+            raise ValueError("loss='ce' needs integer labels")
+        self.loss, self.f, self.C, self.N = loss, feats, int(C), int(N)
+        self.n = int(feats.rows)
+        if self.n < 1 or self.N < 1:
+            raise ValueError('ClientEvaluator needs at least one row and one model')
+        L = _lib.lib()
+        self.block = int(L.fs_z_eval_block_rows())
+        self.ws = torch.empty(int(L.fs_z_eval_ws_doubles(self.n, self.N)), dtype=torch.float64, device=feats.device)
+        ldN = (self.N + 3) // 4 * 4
+        if chunk_rows:
+            blocks = (int(chunk_rows) + self.block - 1) // self.block
+        else:
+            blocks = int(scratch_bytes) // (4 * self.C * ldN) // self.block
+        self.chunk_rows = self.block * max(1, min(blocks, (self.n + self.block - 1) // self.block))
+        self.Z = None
+
+    def _add(self, Z, row0, rows, n_models):
+        L = _lib.lib()
+        if self.loss == 'mse':
+            _lib.check(L.fs_z_eval_add_mse(_lib.ptr(Z), _lib.ptr(self.f.y), self.n, int(row0), int(rows),
+                                           int(n_models), _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                       'fs_z_eval_add_mse')
+        else:
+            _lib.check(L.fs_z_eval_add(_lib.ptr(Z), _lib.ptr(self.f.labels), self.n, int(row0), int(rows),
+                                       int(n_models), self.C, _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                       'fs_z_eval_add')
+
+    def _finish(self, n_models, out):
+        if not (out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 2 * int(n_models)):
+            raise ValueError('out must be a contiguous float64 tensor of [n_models, 2]')
+        _lib.check(_lib.lib().fs_z_eval_finish(_lib.ptr(self.ws), self.ws.numel(), self.n, int(n_models),
+                                               _lib.ptr(out), _lib.stream_ptr()), 'fs_z_eval_finish')
+        return out
+
+    def _check_models(self, n_models):
+        if not 1 <= int(n_models) <= self.N:
+            raise ValueError('n_models must be in [1, %d]' % self.N)
+
+    def run(self, W_all, n_models, out):
+        """``W_all`` [>= n_models, C, ld]: fs_mix_z on row chunks of the features, each reduced by
+        fs_z_eval_add; ``out`` [n_models, 2] float64 (loss, accuracy %).  Current stream."""
+        self._check_models(n_models)
+        ldN = (int(n_models) + 3) // 4 * 4
+        if self.Z is None:
+            self.Z = torch.empty(self.chunk_rows * self.C * ((self.N + 3) // 4 * 4), dtype=torch.float32,
+                                 device=self.f.device)
+        f, L = self.f, _lib.lib()
+        assert self.chunk_rows * self.C * ldN <= self.Z.numel()
+        for row0 in range(0, self.n, self.chunk_rows):
+            rows = min(self.chunk_rows, self.n - row0)
+            _lib.check(L.fs_mix_z(_lib.ptr(W_all), _lib.ptr(f.phi[row0:]), f.ld, int(n_models), self.C, rows,
+                                  _lib.ptr(self.Z), _lib.stream_ptr()), 'fs_mix_z')
+            self._add(self.Z, row0, rows, n_models)
+        return self._finish(n_models, out)
+
+    def run_z(self, Z, n_models, out):
+        """The reduction alone, on logits that already exist: ``Z`` [n, C * ldN(n_models)] in
+        fs_mix_z's layout on this evaluator's rows (FedAMW: the p-solve's Z)."""
+        self._check_models(n_models)
+        ldN = (int(n_models) + 3) // 4 * 4
+        if Z.dtype != torch.float32 or not Z.is_contiguous() or Z.numel() < self.n * self.C * ldN:
+            raise ValueError('Z must be a contiguous float32 tensor of [n, C * ldN]')
+        self._add(Z, 0, self.n, n_models)
+        return self._finish(n_models, out)
+
+
 class Mixture:
     """FedAMW's mixture-weight estimation: Z GEMM + persistent p-SGD (tools.py:435-453).
     ``loss='mse'``: float validation targets, C = 1, fs_mix_solve_mse (one workgroup; the

@@ -23,6 +23,14 @@ Stated choices where the reference is silent or broken: datasets missing from
 (SURVEY.md 8(d) config 1); LIBSVM files that are absent are synthesised in their shape
 (functions/utils.py).  ``clients='parallel'`` (not the reference's semantics) runs FedAvg,
 FedProx and FedAMW with independent clients.
+
+``client_eval`` ('test', 'val' or 'both'; ``--client-eval``) scores every client's local model
+each round (``stats['client_eval']``, functions/tools.py) and adds ``client_test_loss`` /
+``client_test_acc`` (and the ``client_val_*`` pair) to the results: each a list with one entry
+per algorithm in ``name``'s order -- a list over the repeats of [Round, N] arrays (DL and
+FedAMW_OneShot: [N]), or None where the algorithm has no client models (CL), no validation set
+('val' outside FedAMW and FedAMW_OneShot) or was skipped.  The reference's keys and shapes stay
+untouched; without the option the keys are absent.
 """
 import argparse
 import os
@@ -73,7 +81,11 @@ def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None
 
 def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batch_size=32, n_repeats=1,
         alpha_Dirk=0.01, data_dir='../FedAMW/datasets/', result_dir='./results', save=True, clients='sequential',
-        algos=tuple(NAMES), synth=None, verbose=True):
+        algos=tuple(NAMES), synth=None, verbose=True, client_eval=None):
+    if client_eval not in (None, 'test', 'val', 'both'):
+        raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
+    want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
+    cev = {'client_%s_%s' % (w, m): [None] * len(NAMES) for w in want for m in ('loss', 'acc')}
     torch.manual_seed(100)
     np.random.seed(100)
     P = get_parameter(dataset)
@@ -99,6 +111,17 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             timing.setdefault(name, []).append(time.perf_counter() - t0)
             return out
 
+        def ce(name, has_val):
+            """The ``stats`` dict of one algorithm call (None without --client-eval, or when all
+            that was asked for is 'val' and the algorithm has no validation set)."""
+            req = tuple(w for w in want if w == 'test' or has_val)
+            st = {'client_eval': req} if req else None
+            if st is not None:
+                calls.append((NAMES.index(name), st))
+            return st
+
+        calls = []
+
         # exp.py:116-130, positional as the reference calls them; skipped algorithms leave NaN rows
         for k in range(6):
             train_mat[k, :, t] = error_mat[k, :, t] = acc_mat[k, :, t] = np.nan
@@ -108,27 +131,36 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             train_mat[0, :, t], error_mat[0, :, t], acc_mat[0, :, t] = float(r[0]), r[1], r[2]
         if 'DL' in algos:
             r = timed('DL', lambda: tools.Distributed(*a, task, C, D, lr, local_epoch * Round, batch_size, False, 0,
-                                                      False, 0, **kw))
+                                                      False, 0, stats=ce('DL', False), **kw))
             train_mat[1, :, t], error_mat[1, :, t], acc_mat[1, :, t] = float(r[0]), r[1], r[2]
         if 'FedAMW_OneShot' in algos:
             r = timed('FedAMW_OneShot', lambda: tools.FedAMW_OneShot(*a, d['validloader'], task, C, D, lr,
                                                                      local_epoch * Round, batch_size, False, 0, True,
-                                                                     lam_os, Round, lr_p_os, **kw))
+                                                                     lam_os, Round, lr_p_os,
+                                                                     stats=ce('FedAMW_OneShot', True), **kw))
             train_mat[2, :, t], error_mat[2, :, t], acc_mat[2, :, t] = float(r[0]), r[1].numpy(), r[2].numpy()
         if 'FedAvg' in algos:
             r = timed('FedAvg', lambda: tools.FedAvg(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False, 0,
-                                                     Round, **par))
+                                                     Round, stats=ce('FedAvg', False), **par))
             train_mat[3, :, t], error_mat[3, :, t], acc_mat[3, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         if 'FedProx' in algos:
             r = timed('FedProx', lambda: tools.FedProx(*a, task, C, D, lr, local_epoch, batch_size, True, mu, False,
-                                                       0, Round, **par))
+                                                       0, Round, stats=ce('FedProx', False), **par))
             train_mat[4, :, t], error_mat[4, :, t], acc_mat[4, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         if 'FedAMW' in algos:
             r = timed('FedAMW', lambda: tools.FedAMW(*a, d['validloader'], task, C, D, lr, local_epoch, batch_size,
-                                                     False, 0, True, lam, Round, lr_p, **par))
+                                                     False, 0, True, lam, Round, lr_p, stats=ce('FedAMW', True),
+                                                     **par))
             train_mat[5, :, t], error_mat[5, :, t], acc_mat[5, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        for k, st in calls:
+            for key in cev:
+                if key in st:
+                    if cev[key][k] is None:
+                        cev[key][k] = []
+                    cev[key][k].append(st[key].numpy())
     data_ = {'epochs': Round, 'train_loss': train_mat, 'test_loss': error_mat, 'test_acc': acc_mat,
              'heterogeneity': hete_mat, 'name': list(NAMES), 'seconds': {k: list(v) for k, v in timing.items()}}
+    data_.update(cev)
     if save:
         os.makedirs(result_dir, exist_ok=True)
         with open(os.path.join(result_dir, 'exp1_{}.pkl'.format(dataset)), 'wb') as f:
@@ -151,9 +183,11 @@ def main(argv=None):
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES))
     ap.add_argument('--quiet', action='store_true')
+    ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
+                    help="score every client's local model each round on the test / validation rows")
     a = ap.parse_args(argv)
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
-              a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet)
+              a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval)
     for k, name in enumerate(NAMES):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

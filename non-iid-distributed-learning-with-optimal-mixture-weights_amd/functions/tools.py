@@ -26,6 +26,15 @@ Keyword-only extensions (not in the reference):
   GPUs when a torch.distributed process group is initialised.
 * ``stats`` -- a dict that receives the final global model (and, with
   ``stats={'trace': True}``, the global model after every round in ``'W_rounds'``).
+  ``stats={'client_eval': 'test'}`` (or ``'val'``, or ``('test', 'val')``) also scores EVERY
+  client's local model each round, right after local training (chained clients: the chain's
+  state after client j, the reference's ``local_weights[j]``): ``stats['client_test_loss']`` /
+  ``['client_test_acc']`` and / or the ``client_val_*`` pair, CPU float64 tensors [round, N] in
+  the caller's client order ([N] from Distributed and FedAMW_OneShot; Centralized has one model
+  and ignores the key).  ``'val'`` scores on the validloader's rows, so it needs FedAMW or
+  FedAMW_OneShot (ValueError otherwise), where it reuses the p-solve's logits.  One GEMM and one
+  streaming reduction per round (engine.ClientEvaluator, fs_z_eval_*); without the key nothing
+  is launched or allocated, and no generator is touched either way.
 
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
 CPU path.
@@ -142,6 +151,39 @@ def _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round,
         _check_labels([y_val], num_classes, 'validation')
 
 
+def _client_eval_request(stats, has_val):
+    """``stats['client_eval']``: 'test', 'val' or a tuple of both -> the row sets to score every
+    client model on (() without the key).  'val' needs a validation set (FedAMW, FedAMW_OneShot)."""
+    req = None if stats is None else stats.get('client_eval')
+    if req is None:
+        return ()
+    req = (req,) if isinstance(req, str) else tuple(req)
+    for r in req:
+        if r not in ('test', 'val'):
+            raise ValueError("stats['client_eval'] must be 'test', 'val' or ('test', 'val'), got %r" % (r,))
+    if 'val' in req and not has_val:
+        raise ValueError("stats['client_eval'] = 'val' needs a validloader (FedAMW, FedAMW_OneShot)")
+    return tuple(dict.fromkeys(req))
+
+
+def _client_eval_stats(stats, which, hist):
+    """hist [..., N, 2] float64 (any device) -> stats['client_<which>_loss'] / ['client_<which>_acc']."""
+    hist = hist.detach().cpu()
+    stats['client_%s_loss' % which] = hist[..., 0].contiguous()
+    stats['client_%s_acc' % which] = hist[..., 1].contiguous()
+
+
+def _client_eval_once(stats, which, feats, C, N, task, W_out, Z=None):
+    """One set of N local models (Distributed, FedAMW_OneShot) scored on one row set into ``stats``."""
+    ce = engine.ClientEvaluator(feats, C, N, loss=task)
+    out = torch.empty(N, 2, dtype=torch.float64, device=feats.device)
+    if Z is not None:
+        ce.run_z(Z, N, out)
+    else:
+        ce.run(W_out, N, out)
+    _client_eval_stats(stats, which, out)
+
+
 # scheduling options of a Federation (how the launches of the rounds are arranged; none of
 # them changes a result bit):
 #   shuffle_chunk   FedAvg / FedProx with device-replayed shuffles: the shuffles of this many
@@ -168,6 +210,7 @@ class Federation:
         if opts['fedamw_shuffle'] not in ('early', 'late'):
             raise ValueError("fedamw_shuffle must be 'early' or 'late'")
         self.options = opts
+        client_eval = _client_eval_request(stats, validloader is not None)
         # (training labels: only this rank's clients, below -- in sharded mode the other ranks'
         # entries of X_train / y_train need only have the right lengths)
         _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round, y_test,
@@ -246,6 +289,15 @@ class Federation:
         self.loss_hist = torch.empty(R, len(mine), dtype=torch.float64, device=dev)
         self.eval_hist = torch.empty(R, 2, dtype=torch.float64, device=dev)
         self.W_hist = torch.empty(R, C, ld, device=dev) if (stats is not None and stats.get('trace')) else None
+        # stats['client_eval']: every local model of the round scored on the test and / or the
+        # validation rows (engine.ClientEvaluator) into a device history [R][len(mine)][2]
+        self.client_eval = {}
+        for which in client_eval:
+            zs = which == 'val' and self.zshard       # this rank's Z block: L columns, padding clients last
+            ce = engine.ClientEvaluator(self.evaluator.f if which == 'test' else self.mixture.f, C,
+                                        self.L if zs else len(mine), loss=loss)
+            self.client_eval[which] = (ce, torch.zeros(R, len(mine), 2, dtype=torch.float64, device=dev),
+                                       torch.empty(self.L, 2, dtype=torch.float64, device=dev) if zs else None)
         self.n_val_pass = R if algo == 'fedamw' else 0
         self.side = torch.cuda.Stream(device=dev)    # FedAMW validation shuffles of round t+1 run here
         # the native round driver (csrc/round.hip): one call per round phase, training shuffles
@@ -322,6 +374,10 @@ class Federation:
             return out
 
         timed('train', lambda: self.plan.round(t, self.lr, P[0]))
+        if 'test' in self.client_eval:
+            ce, hist, _ = self.client_eval['test']
+            timed('client_eval_test', lambda: ce.run(self.trainer.W_out, len(self.mine), hist[t]))
+        cev = self.client_eval.get('val')
         early = False
         if self.mixture is not None:
             self._train_done = torch.cuda.Event()
@@ -343,6 +399,9 @@ class Federation:
             # cannot read it)
             self.mixture.blocks = (self.nranks if self.nranks > 1 and self.mixture.blocked_covers(self.R) else 1)
             timed('z', lambda: self.mixture.z_block(self.trainer.W_out, self.L, self.Z_local))
+            if cev is not None:       # Z_local is the standard layout at N = L; never the rank-blocked Z
+                timed('client_eval_val', lambda: cev[0].run_z(self.Z_local, self.L, cev[2]))
+                cev[1][t].copy_(cev[2][:len(self.mine)])
             timed('z_allgather', lambda: dist.allgather_z(self.Z_local, self.C, self.mixture.Z,
                                                           blocked=self.mixture.blocks > 1))
             if early:
@@ -354,6 +413,8 @@ class Federation:
         elif self.mixture is not None:
             self.p_hist[t].copy_(self.mixture.p)
             timed('z', lambda: self.mixture.z_block(self.trainer.W_out, self.N, self.mixture.Z))
+            if cev is not None:       # the p-solve's Z: no second GEMM
+                timed('client_eval_val', lambda: cev[0].run_z(self.mixture.Z, self.N, cev[1][t]))
             if early:
                 torch.cuda.current_stream().wait_stream(self.side)
             p = timed('solve', lambda: self.mixture.solve(None, None, self.lr_p, slot=t % 2, z=False))
@@ -404,6 +465,11 @@ class Federation:
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
+            for which, (_, hist, _) in self.client_eval.items():
+                if self.sharded:      # as loss_hist: rank-major rows, then the caller's client order
+                    hist = dist.allgather_rows(hist.permute(1, 0, 2).contiguous(), [len(s) for s in self.shards])
+                    hist = hist[self.inv].permute(1, 0, 2)
+                _client_eval_stats(self.stats, which, hist)
         return train_loss, test_loss, test_acc
 
 
@@ -540,6 +606,7 @@ def Distributed(X_train, y_train, X_test, y_test, type='classification', num_cla
     n_j-weighted aggregate (fs_aggregate, the reference's left fold), one test_loop.  Returns
     (train_loss 0-dim fp32 tensor, test_loss float, test_acc float)."""
     _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, 0, y_test)
+    client_eval = _client_eval_request(stats, False)
     dev = _device()
     C = int(num_classes)
     W_init = init_weights(D, C)
@@ -561,6 +628,8 @@ def Distributed(X_train, y_train, X_test, y_test, type='classification', num_cla
     _print_tests([res], verbose)
     if stats is not None:
         stats.update(W_global=W_g[:, :D].detach().clone())
+    if 'test' in client_eval:
+        _client_eval_once(stats, 'test', ev.f, C, len(ns), task, W_out)
     return train_loss, float(res[0]), float(res[1])
 
 
@@ -581,6 +650,7 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
     Returns (train_loss 0-dim fp32 tensor, test_loss [round], test_acc [round])."""
     _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round, y_test,
                   validloader.dataset.tensors[1])
+    client_eval = _client_eval_request(stats, True)
     dev = _device()
     C, R = int(num_classes), int(round)
     W_init = init_weights(D, C)
@@ -629,4 +699,8 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
         if stats.get('trace'):
             stats['p_rounds'] = p_hist[:R].cpu().numpy()
             stats['W_rounds'] = W_hist[:, :, :D].cpu().numpy()
+    if 'test' in client_eval:
+        _client_eval_once(stats, 'test', ev.f, C, N, task, W_out)
+    if 'val' in client_eval:      # the one Z of the p-solve (fs_mix_z ran in round 0), if there was a round
+        _client_eval_once(stats, 'val', mix.f, C, N, task, W_out, Z=mix.Z if R else None)
     return train_loss, test_loss, test_acc
