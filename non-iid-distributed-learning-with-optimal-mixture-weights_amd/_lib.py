@@ -266,10 +266,11 @@ def stream_ptr(stream=None):
     return C.c_void_p(s.cuda_stream)
 
 
-# the device sources each measured kernel is compiled from (its own file + the headers it includes)
+# the device sources each measured kernel is compiled from (its own file + the headers it includes;
+# local_train's planner and launch setup are host code, csrc/local_train_host.cpp, in no revision)
 KERNEL_SOURCES = {
     'local_train': ('local_train.hip', 'local_train_split.hip', 'local_train_pair.hip', 'local_train_pipe.hip',
-                    'local_train_dbuf.hip', 'split_common.h', 'common.h',
+                    'local_train_dbuf.hip', 'split_common.h', 'local_train_forms.h', 'common.h',
                     'eval_rows.h', 'lanes.h'),
     'mix_solve': ('mixture.hip', 'common.h', 'lanes.h'),
     'mix_z': ('mix_z.hip', 'common.h'),

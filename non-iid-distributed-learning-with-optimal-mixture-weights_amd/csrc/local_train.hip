@@ -22,6 +22,7 @@
 // lane that reads W[c][d] as the forward's B operand, so W never crosses lanes and
 // chained clients (reference semantics) need no inter-lane hand-off.
 #include "common.h"
+#include "local_train_forms.h"
 
 namespace fs {
 
@@ -388,64 +389,18 @@ static int launch_lt(const LTParams& P, int grid, hipStream_t st) {
   return FS_OK;
 }
 
+// one workgroup per client (chained: one workgroup walks them all); fs_local_train's
+// validation and its dispatch over the forms are in local_train_host.cpp
+int launch_local_train_single(const LTParams& P, hipStream_t st) {
+  const int grid = P.chained ? 1 : P.N;
+  const int RT = P.B <= 16 ? 1 : (P.B <= 32 ? 2 : 4);
+  const int CT = P.C <= 16 ? 1 : 2;
+  if (RT == 1 && CT == 1) return launch_lt<1, 1>(P, grid, st);
+  if (RT == 2 && CT == 1) return launch_lt<2, 1>(P, grid, st);
+  if (RT == 4 && CT == 1) return launch_lt<4, 1>(P, grid, st);
+  if (RT == 1 && CT == 2) return launch_lt<1, 2>(P, grid, st);
+  if (RT == 2 && CT == 2) return launch_lt<2, 2>(P, grid, st);
+  return launch_lt<4, 2>(P, grid, st);
+}
+
 }  // namespace fs
-
-using namespace fs;
-
-static thread_local int t_last_lt = 0;
-void fs::set_last_lt_kernel(int k) { t_last_lt = k; }
-extern "C" int fs_local_train_last_kernel(void) { return t_last_lt; }
-
-extern "C" int fs_local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
-                              const int32_t* d_perms, const int32_t* d_order, int N, int C, int B, int E,
-                              float lr, float mu, int prox, float lam, int reg, int chained,
-                              const float* d_W_start, float* d_W_out, double* d_loss, int G, void* d_ws,
-                              int64_t ws_bytes, void* stream) {
-  return fs::local_train(d_phi, ld, d_row_off, d_labels, d_perms, d_order, N, C, B, E, lr, mu, prox, lam, reg, chained,
-                         d_W_start, d_W_out, d_loss, G, d_ws, ws_bytes, reinterpret_cast<hipStream_t>(stream), 0);
-}
-
-int fs::local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
-                    const int32_t* d_perms, const int32_t* d_order, int N, int C, int B, int E, float lr, float mu,
-                    int prox, float lam, int reg, int chained, const float* d_W_start, float* d_W_out,
-                    double* d_loss, int G, void* d_ws, int64_t ws_bytes, hipStream_t st,
-                    int64_t max_client_steps, const FuseEval* fuse) {
-  FS_REQUIRE(N >= 1, "N must be >= 1");
-  FS_REQUIRE(C >= 1 && C <= 32, "num_classes must be in [1, 32]");
-  FS_REQUIRE(B >= 1 && B <= 64, "batch_size must be in [1, 64]");
-  FS_REQUIRE(E >= 0, "epoch must be >= 0");
-  FS_REQUIRE(ld >= 64 && ld % 64 == 0, "ld must be a positive multiple of 64");
-  FS_REQUIRE(d_phi && d_row_off && d_labels && d_perms && d_W_start && d_W_out && d_loss, "null pointer");
-  LTParams P{d_phi, ld, d_row_off, d_labels, d_perms, d_order, N, C, B, E, lr, mu, lam,
-             prox ? 1 : 0, reg ? 1 : 0, chained ? 1 : 0, d_W_start, d_W_out, d_loss, max_client_steps};
-  if (fuse && G > 1 && !chained) {
-    P.fuse_phi = fuse->phi;
-    P.fuse_y = fuse->y;
-    P.fuse_n = fuse->n;
-    P.fuse_E = fuse->E;
-    P.fuse_part = fuse->part;
-  }
-  if (G > 1) {
-    set_last_lt_kernel((G & FS_G_PIPE) ? FS_LT_PIPE : (G & FS_G_PAIR) ? FS_LT_PAIR : (G & FS_G_TEAMS) ? FS_LT_TEAMS : FS_LT_SPLIT);
-    const int rc = (G & FS_G_PIPE)   ? launch_local_train_pipe(P, G & (FS_G_PAIR - 1), d_ws, ws_bytes, st)
-                   : (G & FS_G_PAIR) ? launch_local_train_pair(P, G & (FS_G_PAIR - 1), d_ws, ws_bytes, st)
-                                     : launch_local_train_split(P, G, d_ws, ws_bytes, st);
-    if (rc != FS_OK) return rc;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  set_last_lt_kernel(FS_LT_SINGLE);
-  const int grid = chained ? 1 : N;
-  const int RT = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-  const int CT = C <= 16 ? 1 : 2;
-  int rc;
-  if (RT == 1 && CT == 1) rc = launch_lt<1, 1>(P, grid, st);
-  else if (RT == 2 && CT == 1) rc = launch_lt<2, 1>(P, grid, st);
-  else if (RT == 4 && CT == 1) rc = launch_lt<4, 1>(P, grid, st);
-  else if (RT == 1 && CT == 2) rc = launch_lt<1, 2>(P, grid, st);
-  else if (RT == 2 && CT == 2) rc = launch_lt<2, 2>(P, grid, st);
-  else rc = launch_lt<4, 2>(P, grid, st);
-  if (rc != FS_OK) return rc;
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}

@@ -41,12 +41,6 @@
 
 namespace fs {
 
-constexpr int PR_WAVES = 8;
-constexpr int PR_THREADS = PR_WAVES * 64;
-constexpr int PR_TILES = PR_WAVES;            // 64-column tiles per workgroup and client (one per wave)
-constexpr unsigned PR_SPIN_LIMIT = 1u << 22;
-constexpr int PR_ERR_BYTES = 256;
-
 // In-loop loads are inline asm, invisible to hipcc's vmcnt bookkeeping (which, across this
 // loop's back-edge, drained the whole row stream before every row issue); their waits are
 // counted by hand (PR_WAIT) from the fixed per-half-step issue pattern, and every destination
@@ -565,34 +559,6 @@ __global__ __launch_bounds__(PR_THREADS, 1) void local_train_pair_kernel(LTParam
   if (dead && tid == 0) __hip_atomic_store(X.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-static int pair_rt(int B) { return B <= 16 ? 1 : 2; }
-
-static size_t pair_dyn_lds(int RT) { return sizeof(float) * 2 * (size_t)(RT * 16) * (size_t)(PR_TILES * 64 + 8); }
-
-static size_t pair_static_lds(int RT) {
-  const int NR = RT * 16;
-  return (size_t)PR_WAVES * NR * 16 * 4 + (size_t)NR * 16 * 4 + 2 * NR * 4 + 2 * PR_WAVES * 2 * 4 +
-         PR_WAVES * 4 + 8 + 64;
-}
-
-// can the pair kernel run this shape with groups of G workgroups?
-bool pair_fits(int C, int B, int NT, int G) {
-  if (!(G == 2 || G == 4 || G == 8 || G == 16)) return false;
-  // C <= 14: the two norms travel at classes 14 and 15 of row 0 of the (row, class) hand-off
-  if (C > 14 || B > 32 || NT != PR_TILES * G) return false;
-  const int RT = pair_rt(B);
-  return pair_dyn_lds(RT) + pair_static_lds(RT) <= 160 * 1024;
-}
-
-static int pair_sz(int RT) { return RT * 16 * 16 + 4 >= PR_THREADS ? RT * 16 * 16 + 4 : PR_THREADS; }
-
-// groups in flight: one per G CUs, two clients each
-int pair_groups(int N, int G, int cus) { return std::max(1, std::min((N + 1) / 2, cus / G)); }
-
-int64_t pair_ws_bytes(int N, int G, int B, int cus) {
-  return (int64_t)pair_groups(N, G, cus) * 5 * G * pair_sz(pair_rt(B)) * 8 + PR_ERR_BYTES;
-}
-
 template <int RT, int G, bool PROX>
 static void launch_pair_s(const LTParams& P, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&local_train_pair_kernel<RT, G, PROX>),
@@ -606,46 +572,9 @@ static void launch_pair_g(const LTParams& P, const SplitWS& X, int grid, size_t 
   else launch_pair_s<RT, G, false>(P, X, grid, lds, st);
 }
 
-int launch_local_train_pair(const LTParams& P, int G, void* ws, int64_t ws_bytes, hipStream_t st) {
-  const int RT = pair_rt(P.B);
-  const int NT = (int)(P.ld >> 6);
-  if (P.chained) return fail(FS_EINVAL, "fs_local_train: the pair form needs parallel clients");
-  if (!pair_fits(P.C, P.B, NT, G))
-    return fail(FS_EUNSUPPORTED, "fs_local_train: the pair form needs C <= 14, B <= 32 and ld == 512 G");
-  const int cus = device_cus();
-  if (cus <= 0) return fail(FS_EHIP, "fs_local_train: no device");
-  if (G > cus) return fail(FS_EUNSUPPORTED, "fs_local_train: G exceeds the CU count");
-  const int ng = pair_groups(P.N, G, cus);
-  const int SZ = pair_sz(RT);
-  const int64_t xbytes = (int64_t)ng * 5 * G * SZ * 8;
-  if (!ws || ws_bytes < xbytes + PR_ERR_BYTES) return fail(FS_EINVAL, "fs_local_train: workspace too small");
-  char* base = reinterpret_cast<char*>(ws);
-  SplitWS X;
-  X.xbuf = reinterpret_cast<unsigned long long*>(base);
-  X.err = reinterpret_cast<unsigned*>(base + ws_bytes - PR_ERR_BYTES);
-  X.SZ = SZ;
-  X.ngroups = ng;
-  {
-    const fs_tuning t = tuning();
-    X.spin_limit = t.inject_timeout ? 0u : (t.spin_limit ? t.spin_limit : PR_SPIN_LIMIT);
-  }
-  X.poll_delay = 0;                    // (the pair form polls half a step after publishing)
-  X.stamps = nullptr;
-#ifdef FS_STAMPS
-  X.stamps = reinterpret_cast<unsigned long long*>(base + xbytes);
-#endif
-  // lanes walk ceil(N / 2 ng) clients each
-  const int64_t lane_clients = (P.N + 2 * ng - 1) / (2 * ng);
-  const bool long_launch = P.max_client_steps <= 0 || P.max_client_steps * lane_clients >= (1 << 20) - 1;
-  const unsigned gen = exchange_generation(ws, long_launch);
-  X.tag_base = gen << 20;
-  if (gen <= 1) {
-    hipError_t e = hipMemsetAsync(base, 0, (size_t)xbytes, st);
-    if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_local_train: ") + hipGetErrorString(e));
-  }
-  const size_t lds = pair_dyn_lds(RT);
-  if (P.fuse_E > 0 && ng * G + P.fuse_E > cus) return fail(FS_EINVAL, "fs_local_train: no room for the fused evaluation");
-  const int grid = ng * G + P.fuse_E;
+// the pair form's entry point (local_train_host.cpp has checked the shape and set up X)
+int launch_pair_instance(const LTParams& P, int G, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
+  const int RT = lt_rt(P.B);
 #define FS_PAIR_CASE(rt, g) \
   if (RT == rt && G == g) { launch_pair_g<rt, g>(P, X, grid, lds, st); return FS_OK; }
   FS_PAIR_CASE(2, 2) FS_PAIR_CASE(2, 4) FS_PAIR_CASE(2, 8) FS_PAIR_CASE(2, 16)

@@ -41,15 +41,7 @@
 
 namespace fs {
 
-constexpr int PP_WAVES = 8;
-constexpr int PP_THREADS = PP_WAVES * 64;
-constexpr int PP_TPW = 2;                 // 64-column tiles per wave (the slice is 16 tiles)
-constexpr int PP_NTS = PP_WAVES * PP_TPW;
-constexpr int PP_RS = PP_NTS * 64 + 8;    // LDS image row stride (floats)
-constexpr int PP_NR = 32;                 // batch rows (two 16-row tiles)
-constexpr int PP_SZ = 520;                // granules per (group, parity, slice): [rt][kk][lane] + 2 norms
 constexpr int PP_ZS = 16;                 // transposed partial-logit block: floats per class
-constexpr int PP_ERR_BYTES = 256;
 
 // In-loop loads are inline asm (tagged as the pair form's: `; pr-row`, `; pr-idx`, `; pr-poll`),
 // invisible to hipcc's vmcnt bookkeeping -- which, merging the poll retry loop and the client
@@ -701,20 +693,6 @@ __global__ __launch_bounds__(PP_THREADS, 1) void local_train_pipe_kernel(LTParam
 #endif
 }
 
-bool pipe_fits(int C, int B, int NT, int G, int prox) {
-  (void)prox;
-  if (!(G == 2 || G == 4 || G == 8 || G == 16)) return false;
-  return C >= 1 && C <= 16 && B > 16 && B <= 32 && NT == PP_NTS * G;
-}
-
-static int64_t pipe_xbuf_bytes(int ngroups, int G) { return (int64_t)ngroups * 2 * G * PP_SZ * 8; }
-
-int pipe_groups(int N, int G, int chained, int cus) { return chained ? 1 : std::max(1, std::min(N, cus / G)); }
-
-int64_t pipe_ws_bytes(int N, int G, int chained, int cus) {
-  return pipe_xbuf_bytes(pipe_groups(N, G, chained, cus), G) + PP_ERR_BYTES;
-}
-
 template <int G, bool NRM, bool PROX>
 static void launch_pipe_s(const LTParams& P, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&local_train_pipe_kernel<G, NRM, PROX>),
@@ -729,44 +707,8 @@ static void launch_pipe_g(const LTParams& P, const SplitWS& X, int grid, size_t 
   else launch_pipe_s<G, false, false>(P, X, grid, lds, st);
 }
 
-unsigned split_spin_bound();   // local_train_split.hip: fs_tuning.spin_limit / the test knob
-
-int launch_local_train_pipe(const LTParams& P, int G, void* ws, int64_t ws_bytes, hipStream_t st) {
-  const int NT = (int)(P.ld >> 6);
-  if (!pipe_fits(P.C, P.B, NT, G, P.prox))
-    return fail(FS_EUNSUPPORTED, "fs_local_train: the pipe form needs ld = 1024 G (G = 2, 4, 8 or 16), 16 < B <= 32 "
-                                 "and C <= 16");
-  const int cus = device_cus();
-  if (cus <= 0) return fail(FS_EHIP, "fs_local_train: no device");
-  if (G > cus) return fail(FS_EUNSUPPORTED, "fs_local_train: G exceeds the CU count");
-  const int ng = pipe_groups(P.N, G, P.chained, cus);
-  const int64_t xbytes = pipe_xbuf_bytes(ng, G);
-  if (!ws || ws_bytes < xbytes + PP_ERR_BYTES) return fail(FS_EINVAL, "fs_local_train: workspace too small");
-  char* base = reinterpret_cast<char*>(ws);
-  SplitWS X;
-  X.xbuf = reinterpret_cast<unsigned long long*>(base);
-  X.err = reinterpret_cast<unsigned*>(base + ws_bytes - PP_ERR_BYTES);
-  X.SZ = PP_SZ;
-  X.ngroups = ng;
-  X.spin_limit = split_spin_bound();
-  X.poll_delay = 0;
-  X.stamps = nullptr;
-#ifdef FS_STAMPS
-  X.stamps = reinterpret_cast<unsigned long long*>(base + xbytes);
-#endif
-  // hand-off tags by launch generation (as the split form, local_train_split.hip)
-  const int64_t groups_clients = P.chained ? P.N : (P.N + ng - 1) / ng;
-  const bool long_launch = P.max_client_steps <= 0 || P.max_client_steps * groups_clients >= (1 << 20) - 1;
-  const unsigned gen = exchange_generation(ws, long_launch);
-  X.tag_base = gen << 20;
-  if (gen <= 1) {
-    hipError_t e = hipMemsetAsync(base, 0, (size_t)xbytes, st);
-    if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_local_train: ") + hipGetErrorString(e));
-  }
-  const size_t lds = sizeof(float) * (size_t)PP_NR * PP_RS;
-  if (P.fuse_E > 0 && (P.chained || ng * G + P.fuse_E > cus))
-    return fail(FS_EINVAL, "fs_local_train: no room for the fused evaluation");
-  const int grid = P.chained ? 8 * G : ng * G + P.fuse_E;
+// the pipe form's entry point (local_train_host.cpp has checked the shape and set up X)
+int launch_pipe_instance(const LTParams& P, int G, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
   switch (G) {
     case 2: launch_pipe_g<2>(P, X, grid, lds, st); break;
     case 4: launch_pipe_g<4>(P, X, grid, lds, st); break;

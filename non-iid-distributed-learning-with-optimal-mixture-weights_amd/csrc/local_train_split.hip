@@ -29,11 +29,10 @@
 //                     chain runs on G CUs instead of one.
 // Co-residency: the G partners spin on each other, so the grid never exceeds the CU count;
 // every spin is bounded and a timeout is reported through the workspace error word.
-// Hand-off tags are the group's step counter + 1 (32 bits): the exchange buffer is zeroed by
-// the launcher before every launch.
-#include <mutex>
+// Hand-off tags are the launch generation and the group's step counter + 1 (split_common.h).
+// Host side -- which shapes the form takes, the workspace, the planner, the launch setup:
+// local_train_host.cpp; this file keeps the kernel and the choice of its instance.
 #include <type_traits>
-#include <unordered_map>
 
 #include "common.h"
 #include "eval_rows.h"
@@ -42,10 +41,6 @@
 
 namespace fs {
 
-constexpr int SP_WAVES = 8;
-constexpr int SP_TPW = 2;                 // max 64-column tiles per wave (register budget)
-constexpr unsigned SP_SPIN_LIMIT = 1u << 22;
-constexpr int SP_ERR_BYTES = 256;         // error block at the END of the workspace (never memset)
 // next-step row loads per wave issued ahead of the backward: SP_E1 right after the hand-off,
 // SP_E2 after the S2 barrier, SP_E3 after S3 (the rest inside the backward)
 #ifndef SP_E1
@@ -1011,91 +1006,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
 #endif
 }
 
-#ifndef FS_SPLIT_KERNEL_ONLY   // (scripts/split_asm.sh: one instance's code, without the launchers)
-unsigned exchange_generation(const void* ws, bool long_launch) {
-  static std::mutex gm;
-  static std::unordered_map<const void*, unsigned> gens;
-  std::lock_guard<std::mutex> lk(gm);
-  auto it = gens.find(ws);
-  const unsigned prev = it == gens.end() ? 0u : it->second;
-  const unsigned gen = (long_launch || prev >= 4095u) ? 0u : prev + 1u;
-  gens[ws] = gen;
-  return gen;
-}
-
-static int g_cus = 0;
-
-int device_cus() {
-  if (g_cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) g_cus = 0;
-  }
-  return g_cus;
-}
-
-static size_t split_dyn_lds(int RT, int NT, int G, int teams = 1) {
-  const int tiles = (NT + G - 1) / G;
-  return sizeof(float) * (size_t)teams * (size_t)(RT * 16) * (size_t)(tiles * 64 + 8);
-}
-
-static size_t split_static_lds(int RT, int NW, int teams = 1) {
-  const int NR = RT * 16;
-  return (size_t)teams * ((size_t)NW * NR * 16 * 4 + 2 * (size_t)NR * 16 * 4 + 2 * NR * 4 + NW * 3 * 4 + 8) + 64 +
-         4 * teams;
-}
-
-static int split_rt(int B) { return B <= 16 ? 1 : 2; }
-
-// can G workgroups split one client of this shape (teams = 2: two client lanes of 4 waves per
-// workgroup, parallel clients only)?
-static bool split_fits(int C, int B, int NT, int G, int teams = 1) {
-  if (!(G == 2 || G == 4 || G == 8 || G == 16)) return false;
-  if (C > 16 || B > 32 || NT < G) return false;
-  const int RT = split_rt(B);
-  const int nw = SP_WAVES / teams;
-  const int tiles = (NT + G - 1) / G;
-  if ((tiles + nw - 1) / nw > SP_TPW) return false;
-  if (G >= 8 && RT * 16 * C + 2 > 512) return false;   // exchanged values: at most 512
-  return split_dyn_lds(RT, NT, G, teams) + split_static_lds(RT, nw, teams) <= 160 * 1024;
-}
-
-static int split_sz(int RT) { return RT * 16 * 16 + 4; }
-
-// groups in flight: one per G workgroups, one workgroup per CU (each with `teams` client lanes)
-static int split_groups(int N, int G, int chained, int cus, int teams = 1) {
-  return chained ? 1 : std::max(1, std::min((N + teams - 1) / teams, cus / G));
-}
-
-static int64_t split_xbuf_bytes(int ngroups, int G, int RT, int teams = 1) {
-  return (int64_t)ngroups * teams * 2 * G * split_sz(RT) * 8;
-}
-
-static int64_t split_ws_bytes(int N, int G, int B, int chained, int cus, int teams = 1) {
-  const int RT = split_rt(B);
-  return split_xbuf_bytes(split_groups(N, G, chained, cus, teams), G, RT, teams) + SP_ERR_BYTES;
-}
-
-// s_sleep(1) units before a step's first poll (fs_tuning.split_poll_delay: 0 = by width, -1 =
-// none, n > 0 = n).  By width (profiles/r04/split_poll_delay_*.txt, launch ms): G = 16 (config 5)
-// 5.35-5.37 without, 5.21-5.23 at 16, 5.29-5.31 at 24, 5.45-5.49 at 48; G = 2 (config 2) no gain
-constexpr int SPLIT_PD_WIDE = 16, SPLIT_PD_NARROW = 0;
-static int split_poll_delay(int G, bool chained) {
-  const int t = tuning().split_poll_delay;
-  if (t < 0) return 0;
-  if (t > 0) return t;
-  if (chained) return 0;                 // one group: no other group's polls to yield to
-  return G >= 8 ? SPLIT_PD_WIDE : SPLIT_PD_NARROW;
-}
-
-// the hand-off spin bound (fs_tuning.spin_limit); 0 = the injected-timeout test knob
-static unsigned split_spin_limit() {
-  const fs_tuning t = tuning();
-  if (t.inject_timeout) return 0u;
-  return t.spin_limit ? t.spin_limit : SP_SPIN_LIMIT;
-}
-unsigned split_spin_bound() { return split_spin_limit(); }
-
+#ifndef FS_SPLIT_KERNEL_ONLY   // (scripts/split_asm.sh: one instance's code, without the instance selection)
 template <int RT, int G, bool PROX, int EARLY, int TEAMS, int WAVES = SP_WAVES, int TPWK = SP_TPW, int MBK = 0>
 static void launch_split_k(const LTParams& P, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024)
@@ -1115,7 +1026,7 @@ static void launch_split_k(const LTParams& P, const SplitWS& X, int grid, size_t
 // launch measured the same, profiles/r06/mb_ab.txt), so the 16x16x4 instances stay there
 static int split_mbk(const LTParams& P, int G, int teams) {
   const int t = tuning().split_mb;
-  if (t < 0 || teams != 1 || split_rt(P.B) != 2) return 0;
+  if (t < 0 || teams != 1 || lt_rt(P.B) != 2) return 0;
   const int cb = (P.C + 3) / 4;
   if (t == 0 && cb > 2 && !(cb == 3 && G >= 16)) return 0;
   return cb;
@@ -1213,61 +1124,9 @@ static void launch_split_g(const LTParams& P, const SplitWS& X, int grid, size_t
   else launch_split_s<RT, G, false, 0, 1>(P, X, grid, lds, st);
 }
 
-int launch_local_train_split(const LTParams& P, int Gf, void* ws, int64_t ws_bytes, hipStream_t st) {
-  const int teams = (Gf & FS_G_TEAMS) ? 2 : 1;
-  const int G = Gf & (FS_G_PAIR - 1);
-  if (teams > 1 && (P.chained || !(G == 4 || G == 8)))
-    return fail(FS_EUNSUPPORTED, "fs_local_train: the team form runs parallel clients at G = 4 or 8");
-  const int RT = split_rt(P.B);
-  const int NT = (int)(P.ld >> 6);
-  if (!(G == 2 || G == 4 || G == 8 || G == 16)) return fail(FS_EINVAL, "fs_local_train: G must be 1, 2, 4, 8 or 16");
-  if (P.C > 16 || P.B > 32) return fail(FS_EUNSUPPORTED, "fs_local_train: split clients need C <= 16, B <= 32");
-  if (NT < G) return fail(FS_EUNSUPPORTED, "fs_local_train: fewer feature tiles than workgroups per client");
-  if (!split_fits(P.C, P.B, NT, G, teams)) return fail(FS_EUNSUPPORTED, "fs_local_train: slice too wide for one workgroup");
-  const int cus = device_cus();
-  if (cus <= 0) return fail(FS_EHIP, "fs_local_train: no device");
-  if (G > cus) return fail(FS_EUNSUPPORTED, "fs_local_train: G exceeds the CU count");
-  const int ng = split_groups(P.N, G, P.chained, cus, teams);
-  const int64_t xbytes = split_xbuf_bytes(ng, G, RT, teams);
-  if (!ws || ws_bytes < xbytes + SP_ERR_BYTES) return fail(FS_EINVAL, "fs_local_train: workspace too small");
-  char* base = reinterpret_cast<char*>(ws);
-  SplitWS X;
-  X.xbuf = reinterpret_cast<unsigned long long*>(base);
-  X.err = reinterpret_cast<unsigned*>(base + ws_bytes - SP_ERR_BYTES);   // last block: sticky
-  X.SZ = split_sz(RT);
-  X.ngroups = ng;
-  X.spin_limit = split_spin_limit();
-  X.poll_delay = split_poll_delay(G, P.chained != 0);
-  X.stamps = nullptr;
-#ifdef FS_STAMPS
-  X.stamps = reinterpret_cast<unsigned long long*>(base + xbytes);
-#endif
-  // Hand-off tags: (launch generation << 20) + group step + 1, the generation counted per
-  // workspace on the host, so a granule left by an earlier launch never carries a tag this
-  // launch waits for and the exchange buffer needs no clearing per launch.  It is cleared
-  // when a workspace is first seen, every 4095 launches (the generation wraps) and for a
-  // launch whose groups may run 2^20 - 1 steps or more (then the generation is 0: tags are
-  // the step + 1 alone, as after any clearing).
-  // (groups walk clients in snake order: at most ceil(N / ng) each; chained: all N)
-  const int64_t groups_clients = P.chained ? P.N : (P.N + ng * teams - 1) / (ng * teams);
-  const bool long_launch = P.max_client_steps <= 0 || P.max_client_steps * groups_clients >= (1 << 20) - 1;
-  const unsigned gen = exchange_generation(ws, long_launch);
-  X.tag_base = gen << 20;
-  if (gen <= 1) {                      // first use, wrap or long launch: clear the granules
-    hipError_t e = hipMemsetAsync(base, 0, (size_t)xbytes, st);
-    if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_local_train: ") + hipGetErrorString(e));
-  }
-  const size_t lds = split_dyn_lds(RT, NT, G, teams);
-  if (P.fuse_E > 0 && (P.chained || ng * G + P.fuse_E > cus || lds < sizeof(float) * SP_WAVES * 16 * 17))
-    return fail(FS_EINVAL, "fs_local_train: no room for the fused evaluation");
-  const int grid = P.chained ? 8 * G : ng * G + P.fuse_E;
-  if (teams > 1) {
-    if (RT == 2 && G == 4) { launch_split_teams<2, 4>(P, X, grid, lds, st); return FS_OK; }
-    if (RT == 2 && G == 8) { launch_split_teams<2, 8>(P, X, grid, lds, st); return FS_OK; }
-    if (RT == 1 && G == 4) { launch_split_teams<1, 4>(P, X, grid, lds, st); return FS_OK; }
-    if (RT == 1 && G == 8) { launch_split_teams<1, 8>(P, X, grid, lds, st); return FS_OK; }
-    return fail(FS_EUNSUPPORTED, "fs_local_train: no team kernel for this shape");
-  }
+// the split form's entry point (local_train_host.cpp has checked the shape and set up X)
+int launch_split_instance(const LTParams& P, int G, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
+  const int RT = lt_rt(P.B);
 #define FS_SPLIT_CASE(rt, g) \
   if (RT == rt && G == g) { launch_split_g<rt, g>(P, X, grid, lds, st); return FS_OK; }
   FS_SPLIT_CASE(2, 2) FS_SPLIT_CASE(2, 4) FS_SPLIT_CASE(2, 8) FS_SPLIT_CASE(2, 16)
@@ -1276,143 +1135,15 @@ int launch_local_train_split(const LTParams& P, int Gf, void* ws, int64_t ws_byt
   return fail(FS_EUNSUPPORTED, "fs_local_train: no split kernel for this shape");
 }
 
-int split_idle_cus(int N, int C, int B, int64_t ld, int G, int chained) {
-  const int NT = (int)(ld >> 6);
-  if (G & FS_G_PIPE) {
-    const int g = G & (FS_G_PAIR - 1);
-    const int cus = device_cus();
-    if (chained || cus <= 0 || !pipe_fits(C, B, NT, g, 0)) return 0;
-    return std::max(0, cus - pipe_groups(N, g, 0, cus) * g);
-  }
-  if (G & FS_G_PAIR) {
-    const int g = G & (FS_G_PAIR - 1);
-    const int cus = device_cus();
-    if (chained || cus <= 0 || !pair_fits(C, B, NT, g)) return 0;
-    return std::max(0, cus - pair_groups(N, g, cus) * g);
-  }
-  const int teams = (G & FS_G_TEAMS) ? 2 : 1;
-  G &= FS_G_PAIR - 1;
-  if (chained || G < 2 || C > 16 || B > 32 || !split_fits(C, B, NT, G, teams)) return 0;
-  const int cus = device_cus();
-  if (cus <= 0) return 0;
-  return std::max(0, cus - split_groups(N, G, 0, cus, teams) * G);
+// ... and the team form's
+int launch_teams_instance(const LTParams& P, int G, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
+  const int RT = lt_rt(P.B);
+  if (RT == 2 && G == 4) { launch_split_teams<2, 4>(P, X, grid, lds, st); return FS_OK; }
+  if (RT == 2 && G == 8) { launch_split_teams<2, 8>(P, X, grid, lds, st); return FS_OK; }
+  if (RT == 1 && G == 4) { launch_split_teams<1, 4>(P, X, grid, lds, st); return FS_OK; }
+  if (RT == 1 && G == 8) { launch_split_teams<1, 8>(P, X, grid, lds, st); return FS_OK; }
+  return fail(FS_EUNSUPPORTED, "fs_local_train: no team kernel for this shape");
 }
-
-}  // namespace fs
-
-using namespace fs;
-
-// Plan the launch: G = workgroups per client (1 = one workgroup walks each client; 2..16 =
-// a group of G workgroups splits the feature dimension of one client at a time) and the
-// workspace bytes it needs.  On entry *G_out is a request: 0 = let the planner choose,
-// 1 = one workgroup per client, 2..16 = that group width if the shape allows it (else the
-// planner's choice).
-// prox: the FedProx term is on (kept in the ABI; every split variant covers it).
-// max_en = max_j E * n_j.
-extern "C" int fs_local_train_plan(int N, int C, int B, int E, int64_t ld, int64_t max_en, int chained, int prox,
-                                   int* G_out, int64_t* ws_bytes_out) {
-  FS_REQUIRE(G_out && ws_bytes_out, "null pointer");
-  FS_REQUIRE(N >= 1 && B >= 1 && ld >= 64 && ld % 64 == 0, "bad sizes");
-  const int want = *G_out;
-  *G_out = 1;
-  *ws_bytes_out = 0;
-  const int cus = device_cus();
-  if (want == 1 || C > 16 || B > 32 || cus <= 0) return FS_OK;
-  const int NT = (int)(ld >> 6);
-  // an explicit pipe request
-  if (want & FS_G_PIPE) {
-    const int g = want & (FS_G_PAIR - 1);
-    if (pipe_fits(C, B, NT, g, prox) && g <= cus) {
-      *G_out = g | FS_G_PIPE;
-      *ws_bytes_out = pipe_ws_bytes(N, g, chained, cus);
-      return FS_OK;
-    }
-  }
-  // the pipe form (fs_tuning.split_pipe = 1: wherever it fits; -1 = never; 0 = by shape: parallel
-  // clients at G <= 4 where its groups walk several clients each -- config 4, 1,250 clients of 64
-  // rows on 128 groups of 2: 395-409 vs 419-448 us per launch for the pair form (G = 4) and
-  // 285-302 vs 300-310 us at config 2's 100 clients, where the split form stays
-  // (profiles/r05/pipe_vs_forms.txt); config 5's G = 16: 6.5 vs 4.9 ms, not chosen)
-  // (entered for an automatic choice or a pipe request only: an explicit split, pair or team
-  // request is answered by its own form, never by the pipe form under split_pipe = 1)
-  if ((want == 0 || (want & FS_G_PIPE)) && NT % 16 == 0 && tuning().split_pipe >= 0) {
-    const int g = NT / 16;
-    const bool by_shape = tuning().split_pipe == 0 && want == 0 && tuning().train_form == 0 && !chained &&
-                          !prox && g <= 4 && N > pipe_groups(N, g, 0, cus);
-    if ((tuning().split_pipe > 0 || by_shape) && pipe_fits(C, B, NT, g, prox) && g <= cus) {
-      *G_out = g | FS_G_PIPE;
-      *ws_bytes_out = pipe_ws_bytes(N, g, chained, cus);
-      return FS_OK;
-    }
-  }
-  // an explicit team request
-  if (want & FS_G_TEAMS) {
-    const int g = want & (FS_G_PAIR - 1);
-    if (!chained && (g == 4 || g == 8) && split_fits(C, B, NT, g, 2) && g <= cus) {
-      *G_out = g | FS_G_TEAMS;
-      *ws_bytes_out = split_ws_bytes(N, g, B, 0, cus, 2);
-      return FS_OK;
-    }
-  }
-  // an explicit pair request
-  if (want & FS_G_PAIR) {
-    const int g = want & (FS_G_PAIR - 1);
-    if (!chained && pair_fits(C, B, NT, g) && g <= cus) {
-      *G_out = g | FS_G_PAIR;
-      *ws_bytes_out = pair_ws_bytes(N, g, B, cus);
-      return FS_OK;
-    }
-  }
-  int G = (want > 1 && want < FS_G_PAIR && split_fits(C, B, NT, want) && want <= cus) ? want : 0;
-  // the team form by tuning (fs_tuning.split_teams = 1: wherever it fits, at the narrowest
-  // width; 0 = by shape: not yet chosen automatically; -1 never)
-  if (G == 0 && !chained && tuning().split_teams > 0)
-    for (int cand : {4, 8})
-      if (split_fits(C, B, NT, cand, 2) && cand <= cus) {
-        *G_out = cand | FS_G_TEAMS;
-        *ws_bytes_out = split_ws_bytes(N, cand, B, 0, cus, 2);
-        return FS_OK;
-      }
-  if (G == 0) {
-    if (chained) {
-      // one group walks the chain: slice one step's batch (B x ld floats) to ~32 KB per CU
-      const int64_t bytes = (int64_t)B * ld * 4;
-      for (int cand : {2, 4, 8, 16})
-        if (split_fits(C, B, NT, cand) && cand <= cus) {
-          G = cand;
-          if (bytes / cand <= 32 * 1024) break;
-        }
-    } else {
-      // parallel clients: the narrowest split group that fits (most clients in flight, fewest
-      // partners) -- FedProx too since its anchor is re-read, not register-resident (r02t, prox,
-      // us per launch, G = 1 vs split: config 2 741 / 362, config 3 5955 / 5263, config 4
-      // 580 / 508, config 5 11237 / 7003)
-      for (int cand : {2, 4, 8, 16})
-        if (split_fits(C, B, NT, cand) && cand <= cus) { G = cand; break; }
-      // ... unless the pair form fits and its groups would walk several clients each (where it
-      // measured faster: config 4 0.434 vs 0.457 ms; with one client per group, config 2, the
-      // split form: 0.343 vs 0.366 ms -- profiles/r03/pair_ab.txt) and there is no prox term
-      // (round 5, config 3: split G = 4 5.09-5.11 ms vs pair G = 8 5.24-5.26 and pipe G = 4
-      // 5.25-5.27, profiles/r05/forms_config3_4.txt; round 3 had measured the pair form ahead,
-      // 5.16 vs 5.26), or fs_tuning.train_form asks for it (1: never, 2: wherever it fits)
-      const int form = tuning().train_form;
-      if (form != 1)
-        for (int cand : {2, 4, 8, 16})
-          if (pair_fits(C, B, NT, cand) && cand <= cus &&
-              (form == 2 || G == 0 || (!prox && (int64_t)N > (int64_t)split_groups(N, G, 0, cus)))) {
-            *G_out = cand | FS_G_PAIR;
-            *ws_bytes_out = pair_ws_bytes(N, cand, B, cus);
-            return FS_OK;
-          }
-    }
-  }
-  (void)max_en;
-  (void)E;
-  if (G == 0) return FS_OK;
-  *G_out = G;
-  *ws_bytes_out = split_ws_bytes(N, G, B, chained, cus);
-  return FS_OK;
-}
-#else
-}  // namespace fs
 #endif
+
+}  // namespace fs

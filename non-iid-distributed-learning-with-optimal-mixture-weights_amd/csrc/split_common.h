@@ -1,30 +1,19 @@
-// Pieces shared by the split-client (local_train_split.hip) and pair-client
-// (local_train_pair.hip) local-training kernels: the exchange workspace, the LDS image
-// layout of one step's batch slice, and the walk of a group's client sequence.
+// Pieces shared by the exchanging local-training kernels -- split (local_train_split.hip,
+// local_train_dbuf.hip), pair (local_train_pair.hip) and pipe (local_train_pipe.hip): the exchange
+// workspace, the LDS image layout of one step's batch slice, and the walk of a group's client
+// sequence.  Their host side (geometry, planner, workspace layout, hand-off tags, launch setup)
+// is local_train_host.cpp; local_train_forms.h holds what the two sides share.
 #pragma once
 
 #include "common.h"
+#include "local_train_forms.h"
 
 namespace fs {
 
-int device_cus();   // CUs of the current device (cached)
-
-// Hand-off tags of an exchanging launch: (launch generation << 20) + step + 1, the generation
-// counted per workspace on the host, so a granule left by an earlier launch never carries a
-// tag this launch waits for and the exchange buffer needs no clearing per launch.  0 (the
-// caller then clears the granules): a workspace's first use, every 4095 launches (the
-// generation wraps), and a launch whose client sequences may run 2^20 - 1 steps or more.
-unsigned exchange_generation(const void* ws, bool long_launch);
-
-// the pair form (local_train_pair.hip)
-bool pair_fits(int C, int B, int NT, int G);
-// the pipe form (local_train_pipe.hip)
-bool pipe_fits(int C, int B, int NT, int G, int prox);
-int pipe_groups(int N, int G, int chained, int cus);
-int64_t pipe_ws_bytes(int N, int G, int chained, int cus);
-int pair_groups(int N, int G, int cus);
-int64_t pair_ws_bytes(int N, int G, int B, int cus);
-
+// The exchange workspace of one launch (filled by local_train_host.cpp's exchange setup).
+// Hand-off tags: (launch generation << 20) + step + 1, the generation counted per workspace on
+// the host, so a granule left by an earlier launch never carries a tag this launch waits for
+// and the exchange buffer needs no clearing per launch.
 struct SplitWS {
   unsigned* err;                       // [1] sticky; nonzero: a partner never arrived (spin bound hit)
   unsigned long long* xbuf;            // [ngroups][2][G][SZ] published partials: {tag, value} granules

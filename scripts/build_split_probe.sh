@@ -24,9 +24,9 @@ cd $T
 H="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -munsafe-fp-atomics"
 mkdir -p build
 $H -DFS_STAMPS -c local_train_split.hip -o build/lts.o
-objs=""
-for f in local_train local_train_pair aggregate eval mixture mix_z randperm round feature_map gram; do
-  objs="$objs $PKG/csrc/build/$f.o"
-done
-$H -shared -o $PKG/libfedsim_split_probe_stamps.so build/lts.o $objs $PKG/csrc/build/host.o $PKG/csrc/build/libsvm.o -lpthread
+# (the launch setup places the stamps in the workspace: the host file with the stamps too)
+$H -DFS_STAMPS -x hip --offload-host-only -c $PKG/csrc/local_train_host.cpp -o build/lth.o
+# every other object as the library has it (make -C <pkg>/csrc first)
+objs=$(ls $PKG/csrc/build/*.o | grep -v -e /local_train_split.o -e /local_train_host.o -e variant_ -e _stamps -e _probe)
+$H -shared -o $PKG/libfedsim_split_probe_stamps.so build/lts.o build/lth.o $objs -lpthread
 echo built $PKG/libfedsim_split_probe_stamps.so
