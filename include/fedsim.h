@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 18
+#define FS_ABI_VERSION 19
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -346,6 +346,47 @@ int fs_z_eval_add(const float* d_Z, const int32_t* d_labels, int n, int row0, in
 int fs_z_eval_add_mse(const float* d_Z, const float* d_y, int n, int row0, int rows, int N, double* d_ws,
                       int64_t ws_doubles, void* stream);
 int fs_z_eval_finish(const double* d_ws, int64_t ws_doubles, int n, int N, double* d_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 19) Local evaluation: the test_loop metrics (tools.py:218-237) of a model on EVERY
+ * client's OWN training rows, in one pass over the resident features d_phi (CSR by client:
+ * client j owns rows [d_row_off[j], d_row_off[j+1]), int64 [N + 1] on the device).  The
+ * reference never reports them: its train_loop keeps a running train_acc.avg (tools.py:213-215)
+ * while the weights move, and every caller drops it.  For every client j < N, with
+ * n_j = d_row_off[j+1] - d_row_off[j] and the model W_j = d_W + j * w_stride (C rows of ld floats):
+ *   d_out[2j]   = mean cross-entropy of W_j over the client's n_j rows
+ *   d_out[2j+1] = 100 * correct / n_j, top-1, ties to the lowest class index
+ * -- fs_eval's definitions.  w_stride = 0 scores ONE model (the global one) on every client: the
+ * per-client distribution of the aggregated model, and sum_j (n_j / n) d_out[2j] is the true
+ * objective F(W_g).  w_stride = C * ld scores the clients x params buffer: W_out[j] on client j,
+ * the local model on local data.  w_stride must be a multiple of 4 floats.
+ *   contract A (bitwise)  d_out[2j..2j+1] equals what fs_eval returns for (d_phi +
+ *                         d_row_off[j] * ld, d_labels + d_row_off[j], n_j, W_j) -- so a client's
+ *                         result does not depend on N, on its position or on its neighbours
+ * One 8-wave workgroup per 16-row group counted from the client's first row (client j owns
+ * ceil(n_j / 16) groups) runs fs_eval's group body and writes its fp64 partial pair to the
+ * workspace; one 256-thread workgroup per client then folds that client's partials with fs_eval's
+ * finaliser arithmetic and divides by n_j.  A workgroup finds its client by binary search in the
+ * prefix of group counts, which a one-workgroup pre-kernel writes into the head of the workspace
+ * from d_row_off.  Three launches on `stream`; the call is asynchronous, allocates nothing, copies
+ * nothing from the host and never synchronises; no atomics, no cross-workgroup wait.
+ * h_n [N] (HOST, int64; the n_j above, each >= 1) sizes the grid and is read during the call
+ * only.  1 <= C <= 32, ld % 64 == 0; any N whose group count fits 31 bits.
+ * d_ws: fs_eval_clients_ws_doubles(total_rows, N) doubles, total_rows = sum_j n_j:
+ *   (N + 2) / 2  +  2 * (total_rows / 16 + N)      (integer divisions)
+ * -- N + 1 int32 prefix entries, then one pair per group, of which there are at most
+ * total_rows / 16 + N.  The workspace holds nothing between calls.
+ * fs_eval_clients_mse: the same under nn.MSELoss at one output column (C = 1, d_y float targets
+ * by row, W_j = d_W + j * w_stride of ld floats): fs_eval_mse's definitions and row body, held to
+ * fs_eval_mse on the slices bit for bit.
+ * ------------------------------------------------------------------------- */
+int64_t fs_eval_clients_ws_doubles(int64_t total_rows, int N);
+int fs_eval_clients(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int64_t* h_n,
+                    const int32_t* d_labels, int N, const float* d_W, int64_t w_stride, int C, double* d_out,
+                    double* d_ws, int64_t ws_doubles, void* stream);
+int fs_eval_clients_mse(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int64_t* h_n,
+                        const float* d_y, int N, const float* d_W, int64_t w_stride, double* d_out, double* d_ws,
+                        int64_t ws_doubles, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * FedAMW mixture step 1: Z[v][c*ldN + n] = sum_d X_val[v][d] * W_n[c][d], where

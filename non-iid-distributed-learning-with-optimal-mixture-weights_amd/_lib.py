@@ -50,6 +50,11 @@ _SIGS = {
     'fs_z_eval_add_mse': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_int64, C.c_void_p]),
     'fs_z_eval_finish': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'fs_eval_clients_ws_doubles': (C.c_int64, [C.c_int64, C.c_int]),
+    'fs_eval_clients': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_eval_clients_mse': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'fs_mix_z': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                            C.c_void_p]),
     'fs_mix_solve_ws_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
@@ -87,7 +92,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)

@@ -481,6 +481,53 @@ class ClientEvaluator:
         return self._finish(n_models, out)
 
 
+class LocalEvaluator:
+    """Local evaluation (fs_eval_clients): the (loss, accuracy %) of a model on every client's
+    OWN rows of a resident training ``Features`` (shared with its owner, a ``LocalTrainer``'s
+    ``.f``), one pass over the features instead of N fs_eval calls on row slices.
+
+    ``run(W, stride, out)``: client j's model is ``W`` + j * ``stride`` floats -- stride 0 scores
+    one model (the global one) on every client, stride C * ld the clients x params buffer
+    (``W_out[j]`` on client j).  Owns the workspace.  A client's two numbers are bitwise what
+    ``Evaluator.run`` gives on its row slice (include/fedsim.h, contract A)."""
+
+    def __init__(self, feats, C, loss='ce'):
+        if loss not in ('ce', 'mse'):
+            raise ValueError("loss must be 'ce' or 'mse'")
+        if loss == 'mse' and (int(C) != 1 or feats.y is None):
+            raise ValueError("loss='mse' needs C == 1 and Features(float_targets=True)")
+        if loss == 'ce' and feats.labels is None:
+            raise ValueError("loss='ce' needs integer labels")
+        self.loss, self.f, self.C = loss, feats, int(C)
+        self.N = int(len(feats.ns))
+        if self.N < 1 or int(feats.ns.min()) < 1:
+            raise ValueError('LocalEvaluator needs at least one client and one row per client')
+        self._h_n = np.ascontiguousarray(feats.ns, dtype=np.int64)
+        self.ws = torch.empty(int(_lib.lib().fs_eval_clients_ws_doubles(int(feats.rows), self.N)),
+                              dtype=torch.float64, device=feats.device)
+
+    def run(self, W, stride, out):
+        """``out`` [N, 2] float64 (loss, accuracy %) on the current stream."""
+        stride = int(stride)
+        need = (self.N - 1) * stride + self.C * self.f.ld
+        if W.dtype != torch.float32 or not W.is_contiguous() or W.numel() < need:
+            raise ValueError('W must be a contiguous float32 tensor of at least %d floats' % need)
+        if not (out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= 2 * self.N):
+            raise ValueError('out must be a contiguous float64 tensor of [N, 2]')
+        f, L = self.f, _lib.lib()
+        if self.loss == 'mse':
+            _lib.check(L.fs_eval_clients_mse(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), self._h_n.ctypes.data,
+                                             _lib.ptr(f.y), self.N, _lib.ptr(W), stride, _lib.ptr(out),
+                                             _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                       'fs_eval_clients_mse')
+        else:
+            _lib.check(L.fs_eval_clients(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), self._h_n.ctypes.data,
+                                         _lib.ptr(f.labels), self.N, _lib.ptr(W), stride, self.C, _lib.ptr(out),
+                                         _lib.ptr(self.ws), self.ws.numel(), _lib.stream_ptr()),
+                       'fs_eval_clients')
+        return out
+
+
 class Mixture:
     """FedAMW's mixture-weight estimation: Z GEMM + persistent p-SGD (tools.py:435-453).
     ``loss='mse'``: float validation targets, C = 1, fs_mix_solve_mse (one workgroup; the

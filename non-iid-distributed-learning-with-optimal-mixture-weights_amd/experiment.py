@@ -31,6 +31,12 @@ per algorithm in ``name``'s order -- a list over the repeats of [Round, N] array
 FedAMW_OneShot: [N]), or None where the algorithm has no client models (CL), no validation set
 ('val' outside FedAMW and FedAMW_OneShot) or was skipped.  The reference's keys and shapes stay
 untouched; without the option the keys are absent.
+
+``local_eval`` ('global', 'own' or 'both'; ``--local-eval``) scores the round's global model
+and / or every client's own model on each client's OWN training rows (``stats['local_eval']``)
+and adds ``local_global_loss`` / ``local_global_acc`` / ``global_objective`` and the
+``local_own_*`` pair in the same per-algorithm list form (``global_objective``: [Round]; DL:
+[N] and a 0-dim objective; FedAMW_OneShot: 'own' [N]); None for CL, which pools the clients.
 """
 import argparse
 import os
@@ -81,11 +87,17 @@ def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None
 
 def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batch_size=32, n_repeats=1,
         alpha_Dirk=0.01, data_dir='../FedAMW/datasets/', result_dir='./results', save=True, clients='sequential',
-        algos=tuple(NAMES), synth=None, verbose=True, client_eval=None):
+        algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
+    if local_eval not in (None, 'global', 'own', 'both'):
+        raise ValueError("local_eval must be None, 'global', 'own' or 'both'")
+    lwant = {None: (), 'both': ('global', 'own')}.get(local_eval, (local_eval,))
     want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
     cev = {'client_%s_%s' % (w, m): [None] * len(NAMES) for w in want for m in ('loss', 'acc')}
+    cev.update({'local_%s_%s' % (w, m): [None] * len(NAMES) for w in lwant for m in ('loss', 'acc')})
+    if 'global' in lwant:
+        cev['global_objective'] = [None] * len(NAMES)
     torch.manual_seed(100)
     np.random.seed(100)
     P = get_parameter(dataset)
@@ -112,10 +124,13 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             return out
 
         def ce(name, has_val):
-            """The ``stats`` dict of one algorithm call (None without --client-eval, or when all
-            that was asked for is 'val' and the algorithm has no validation set)."""
+            """The ``stats`` dict of one algorithm call (None without --client-eval / --local-eval,
+            or when all that was asked for is 'val' and the algorithm has no validation set)."""
             req = tuple(w for w in want if w == 'test' or has_val)
-            st = {'client_eval': req} if req else None
+            st = {'client_eval': req} if req else {}
+            if lwant:
+                st['local_eval'] = lwant
+            st = st or None
             if st is not None:
                 calls.append((NAMES.index(name), st))
             return st
@@ -185,9 +200,12 @@ def main(argv=None):
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
+    ap.add_argument('--local-eval', default=None, choices=['global', 'own', 'both'],
+                    help="score the round's global model / every client's own model on each client's own rows")
     a = ap.parse_args(argv)
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
-              a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval)
+              a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval,
+              local_eval=a.local_eval)
     for k, name in enumerate(NAMES):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

@@ -35,6 +35,20 @@ Keyword-only extensions (not in the reference):
   FedAMW_OneShot (ValueError otherwise), where it reuses the p-solve's logits.  One GEMM and one
   streaming reduction per round (engine.ClientEvaluator, fs_z_eval_*); without the key nothing
   is launched or allocated, and no generator is touched either way.
+  ``stats={'local_eval': 'global'}`` (or ``'own'``, or ``('global', 'own')``) scores models on
+  every client's OWN training rows each round (engine.LocalEvaluator, fs_eval_clients: one pass
+  over the resident features).  ``'global'``: the round's aggregated model (FedAMW: the
+  p-weighted one; the model ``test_loss[t]`` scores) on each client ->
+  ``stats['local_global_loss']`` / ``['local_global_acc']``, and the true objective
+  ``stats['global_objective']`` = sum_j (n_j / n) local_global_loss[:, j] (float64, client
+  order) -- which ``train_loss`` is not: that is a running mean over the last local epoch, taken
+  while the weights move, with the prox and ridge terms.  ``'own'``: each client's own trained
+  model, right after local training (the reference's dropped ``train_acc.avg``,
+  tools.py:213-215, but of the finished model) -> ``stats['local_own_loss']`` /
+  ``['local_own_acc']``.  CPU float64 tensors [round, N] in the caller's client order
+  (Distributed: [N]; FedAMW_OneShot: 'global' [round, N], 'own' [N]); Centralized pools the
+  clients into one and raises a ValueError.  Nothing is drawn from any generator and the
+  returns are bitwise those of the run without the key.
 
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
 CPU path.
@@ -184,6 +198,41 @@ def _client_eval_once(stats, which, feats, C, N, task, W_out, Z=None):
     _client_eval_stats(stats, which, out)
 
 
+def _local_eval_request(stats):
+    """``stats['local_eval']``: 'global', 'own' or a tuple of both -> the model sets to score on
+    every client's own rows (() without the key)."""
+    req = None if stats is None else stats.get('local_eval')
+    if req is None:
+        return ()
+    req = (req,) if isinstance(req, str) else tuple(req)
+    for r in req:
+        if r not in ('global', 'own'):
+            raise ValueError("stats['local_eval'] must be 'global', 'own' or ('global', 'own'), got %r" % (r,))
+    return tuple(dict.fromkeys(req))
+
+
+def _local_eval_stats(stats, which, hist, ns):
+    """hist [..., N, 2] float64 (any device, the caller's client order) -> stats['local_<which>_loss']
+    / ['local_<which>_acc']; 'global' also gives stats['global_objective'], the n_j-weighted sum
+    of the losses in float64, client by client."""
+    hist = hist.detach().cpu()
+    loss = stats['local_%s_loss' % which] = hist[..., 0].contiguous()
+    stats['local_%s_acc' % which] = hist[..., 1].contiguous()
+    if which == 'global':
+        w = np.asarray(ns, dtype=np.float64) / float(np.sum(ns))
+        obj = torch.zeros(loss.shape[:-1], dtype=torch.float64)
+        for j in range(loss.shape[-1]):
+            obj += float(w[j]) * loss[..., j]
+        stats['global_objective'] = obj
+
+
+def _local_eval_once(stats, which, le, W, stride):
+    """One model set scored once on every client's own rows (Distributed, FedAMW_OneShot 'own')."""
+    out = torch.empty(le.N, 2, dtype=torch.float64, device=le.f.device)
+    le.run(W, stride, out)
+    _local_eval_stats(stats, which, out, le.f.ns)
+
+
 # scheduling options of a Federation (how the launches of the rounds are arranged; none of
 # them changes a result bit):
 #   shuffle_chunk   FedAvg / FedProx with device-replayed shuffles: the shuffles of this many
@@ -211,6 +260,7 @@ class Federation:
             raise ValueError("fedamw_shuffle must be 'early' or 'late'")
         self.options = opts
         client_eval = _client_eval_request(stats, validloader is not None)
+        local_eval = _local_eval_request(stats)
         # (training labels: only this rank's clients, below -- in sharded mode the other ranks'
         # entries of X_train / y_train need only have the right lengths)
         _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round, y_test,
@@ -298,6 +348,11 @@ class Federation:
                                         self.L if zs else len(mine), loss=loss)
             self.client_eval[which] = (ce, torch.zeros(R, len(mine), 2, dtype=torch.float64, device=dev),
                                        torch.empty(self.L, 2, dtype=torch.float64, device=dev) if zs else None)
+        # stats['local_eval']: the round's global model and / or every client's own model scored
+        # on this rank's clients' own rows (engine.LocalEvaluator) into device histories [R][len(mine)][2]
+        self.local_eval = engine.LocalEvaluator(self.feats, C, loss=loss) if local_eval else None
+        self.local_hist = {which: torch.zeros(R, len(mine), 2, dtype=torch.float64, device=dev)
+                           for which in local_eval}
         self.n_val_pass = R if algo == 'fedamw' else 0
         self.side = torch.cuda.Stream(device=dev)    # FedAMW validation shuffles of round t+1 run here
         # the native round driver (csrc/round.hip): one call per round phase, training shuffles
@@ -377,6 +432,9 @@ class Federation:
         if 'test' in self.client_eval:
             ce, hist, _ = self.client_eval['test']
             timed('client_eval_test', lambda: ce.run(self.trainer.W_out, len(self.mine), hist[t]))
+        if 'own' in self.local_hist:
+            timed('local_eval_own', lambda: self.local_eval.run(self.trainer.W_out, self.C * self.ld,
+                                                                self.local_hist['own'][t]))
         cev = self.client_eval.get('val')
         early = False
         if self.mixture is not None:
@@ -426,6 +484,9 @@ class Federation:
             self.plan.round(t, self.lr, P[2])
         else:
             self.plan.round(t, self.lr, P[1] | P[2])
+        if 'global' in self.local_hist:     # the W_g that test_loss[t] scores (read only: a deferred test
+            # evaluation, which reads it in round t+1's training launch, is not disturbed)
+            timed('local_eval_global', lambda: self.local_eval.run(self.W_g, 0, self.local_hist['global'][t]))
         if self.W_hist is not None:
             self.W_hist[t].copy_(self.W_g)
         self.t += 1
@@ -470,6 +531,11 @@ class Federation:
                     hist = dist.allgather_rows(hist.permute(1, 0, 2).contiguous(), [len(s) for s in self.shards])
                     hist = hist[self.inv].permute(1, 0, 2)
                 _client_eval_stats(self.stats, which, hist)
+            for which, hist in self.local_hist.items():
+                if self.sharded:      # each rank scored its own shard: gather, then the caller's client order
+                    hist = dist.allgather_rows(hist.permute(1, 0, 2).contiguous(), [len(s) for s in self.shards])
+                    hist = hist[self.inv].permute(1, 0, 2)
+                _local_eval_stats(self.stats, which, hist, self.ns)
         return train_loss, test_loss, test_acc
 
 
@@ -579,6 +645,9 @@ def Centralized(X_train, y_train, X_test, y_test, type='classification', num_cla
     ``epoch`` epochs (exp.py:116 passes local_epoch * Round), one test_loop.  Returns
     (train_loss, test_loss, test_acc) as Python floats, like the reference's Meter averages."""
     _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, 0, y_test)
+    if _local_eval_request(stats):
+        raise ValueError("stats['local_eval'] has no meaning for Centralized: the clients' rows are pooled into one "
+                         "client, so there are no per-client rows to score on")
     dev = _device()
     C = int(num_classes)
     W_init = init_weights(D, C)
@@ -607,6 +676,7 @@ def Distributed(X_train, y_train, X_test, y_test, type='classification', num_cla
     (train_loss 0-dim fp32 tensor, test_loss float, test_acc float)."""
     _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, 0, y_test)
     client_eval = _client_eval_request(stats, False)
+    local_eval = _local_eval_request(stats)
     dev = _device()
     C = int(num_classes)
     W_init = init_weights(D, C)
@@ -630,6 +700,12 @@ def Distributed(X_train, y_train, X_test, y_test, type='classification', num_cla
         stats.update(W_global=W_g[:, :D].detach().clone())
     if 'test' in client_eval:
         _client_eval_once(stats, 'test', ev.f, C, len(ns), task, W_out)
+    if local_eval:
+        le = engine.LocalEvaluator(feats, C, loss=task)
+        if 'global' in local_eval:
+            _local_eval_once(stats, 'global', le, W_g, 0)
+        if 'own' in local_eval:
+            _local_eval_once(stats, 'own', le, W_out, C * ld)
     return train_loss, float(res[0]), float(res[1])
 
 
@@ -651,6 +727,7 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
     _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round, y_test,
                   validloader.dataset.tensors[1])
     client_eval = _client_eval_request(stats, True)
+    local_eval = _local_eval_request(stats)
     dev = _device()
     C, R = int(num_classes), int(round)
     W_init = init_weights(D, C)
@@ -675,6 +752,8 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
     eval_hist = torch.empty(max(R, 1), 2, dtype=torch.float64, device=dev)
     p_hist = torch.empty(max(R, 1), N, dtype=torch.float32, device=dev)
     W_hist = torch.empty(R, C, ld, device=dev) if (stats is not None and stats.get('trace')) else None
+    le = engine.LocalEvaluator(feats, C, loss=task) if local_eval else None
+    lg_hist = torch.zeros(R, N, 2, dtype=torch.float64, device=dev) if 'global' in local_eval else None
     for t in range(R):
         seeds = rng.draw_pass_seeds(2)          # the validation pass, then test_loop's pass
         mix.solve(W_out, seeds[:1], lr_p, z=(t == 0))
@@ -687,6 +766,8 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
         if W_hist is not None:
             W_hist[t].copy_(W_g)
         ev.run(W_g, eval_hist[t])
+        if lg_hist is not None:
+            le.run(W_g, 0, lg_hist[t])
     trainer.check_errors()
     mix.check_errors()
     train_loss = torch.sum(p0 * torch.tensor([float(v) for v in loss.cpu().numpy()]))   # tools.py:292
@@ -703,4 +784,8 @@ def FedAMW_OneShot(X_train, y_train, X_test, y_test, validloader, type='classifi
         _client_eval_once(stats, 'test', ev.f, C, N, task, W_out)
     if 'val' in client_eval:      # the one Z of the p-solve (fs_mix_z ran in round 0), if there was a round
         _client_eval_once(stats, 'val', mix.f, C, N, task, W_out, Z=mix.Z if R else None)
+    if lg_hist is not None:
+        _local_eval_stats(stats, 'global', lg_hist, ns)
+    if 'own' in local_eval:
+        _local_eval_once(stats, 'own', le, W_out, C * ld)
     return train_loss, test_loss, test_acc
