@@ -53,6 +53,44 @@ namespace fs {
 #define SP_E3 0
 #endif
 constexpr int SP_EARLY = SP_E1 + SP_E2 + SP_E3;
+// The 16x16x4 early instance at G = 2 (config 2, round 8): where the backward issues the wave's
+// 12 remaining next-step row loads, and when it reads its image rows.  Left to hipcc, the loads of
+// tile 1's backward sank behind the tile's last MFMAs (after backward MFMA 61-63 of 64, not 36-48
+// as written) onto the dead gradient accumulators, and every image row was read just in time
+// (ds_read_b128, lgkmcnt(0), 4 MFMAs).  SP_BWD_FENCE ends every backward iteration with a scheduling
+// fence, so each load goes out in the iteration the source names, into registers of its own
+// (scripts/lt_issue_points.py lists the compiled issue points; tests/test_split_schedule.py).
+//   SP_BWD_PF        the image row of iteration kk + 1 is read ahead of iteration kk's MFMAs
+//   SP_BWD_NUM/_DEN  the stream's head: loads per backward iteration (1/1: one each)
+//   SP_BWD_TAIL/_TAILPER  its last TAIL loads go out TAILPER per iteration at the backward's end
+//   SP_EG2           the early depth at G = 2
+// Shipped: read-ahead, tile 0's last four loads one per iteration (the pre-forward needs them), tile
+// 1's eight in one burst behind the backward's last MFMA.  Config 2, us per launch (profiles/r08/):
+// as hipcc placed them 277; pinned where the source had them (1/1, no tail) 285, with read-ahead
+// 275; the burst at the end alone 278, with read-ahead 267.  Once the image reads no longer pace
+// the backward its MFMAs do, and a row load between them costs issue slots.  Same arithmetic in
+// the same order either way: bitwise the same results.  SP_BWD_FENCE = 0 is the earlier code.
+#ifndef SP_BWD_FENCE
+#define SP_BWD_FENCE 1
+#endif
+#ifndef SP_BWD_NUM
+#define SP_BWD_NUM 1
+#endif
+#ifndef SP_BWD_DEN
+#define SP_BWD_DEN 1
+#endif
+#ifndef SP_BWD_PF
+#define SP_BWD_PF 1
+#endif
+#ifndef SP_EG2
+#define SP_EG2 4
+#endif
+#ifndef SP_BWD_TAIL
+#define SP_BWD_TAIL 8
+#endif
+#ifndef SP_BWD_TAILPER
+#define SP_BWD_TAILPER 8
+#endif
 // mb instances: the backward's image and g words read one row block ahead (SP_MB_BWD_PF; without
 // it the reads waited just in time: config 2 313 -> 288 us per launch, config 5 5.99 -> 5.58 ms,
 // profiles/r06/mb_ab.txt), and the next step's tile-0 forward at the step's end (SP_MB_PRE, where
@@ -904,14 +942,42 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
             for (int kk = 0; kk < 4 * RT; ++kk) xpre[kk] = ld4(((kk & 1) ? ib1 : ib0) + 4 * kk * RSx);
             __builtin_amdgcn_sched_barrier(0);
           }
+          // FENCED (G = 2, see SP_BWD_FENCE): the in-backward loads pinned to their iterations
+          // (RT = 1, the other widths and the prox instances show the same sinking and are left as they
+          // compile until each is measured at its own shape: profiles/r08/issue_points_other_16x16x4.txt)
+          constexpr bool FENCED =
+              SP_BWD_FENCE && RT == 2 && G == 2 && !PROX && TEAMS == 1 && TPW > 1 && EAN > 0 && EAN < NLD;
+          constexpr bool PF = FENCED && SP_BWD_PF;
+          float4 xn = zero4;
+          if constexpr (PF) xn = ld4(ib0);
 #pragma unroll
           for (int kk = 0; kk < 4 * RT; ++kk) {
-            const float4 x = TPW == 1 ? xpre[kk] : ld4(((kk & 1) ? ib1 : ib0) + 4 * kk * RSx);
+            float4 x;
+            if constexpr (PF) {
+              x = xn;
+              if (kk + 1 < 4 * RT) xn = ld4((((kk + 1) & 1) ? ib1 : ib0) + 4 * (kk + 1) * RSx);
+              __builtin_amdgcn_sched_barrier(0);
+            } else {
+              x = TPW == 1 ? xpre[kk] : ld4(((kk & 1) ? ib1 : ib0) + 4 * kk * RSx);
+            }
 #pragma unroll
             for (int e4 = 0; e4 < 4; ++e4) ga[e4] = mfma4(comp(x, e4), gB[kk], ga[e4]);
             if constexpr (decltype(LD)::value) {
               if constexpr (EAN == 0) {
                 xf[i][kk >> 2][kk & 3] = ld4(P.phi + (int64_t)pn[kk >> 2] * ld + 64 * t0 + 4 * lg + 64 * Tl + 16 * (kk & 3));
+              } else if constexpr (FENCED) {
+                // load f goes out in iteration itf: the stream's head at SP_BWD_NUM / SP_BWD_DEN loads per
+                // iteration, its last SP_BWD_TAIL loads SP_BWD_TAILPER per iteration at the backward's end
+                // (f and it are constants after unrolling)
+                constexpr int NIT = TPW * 4 * RT;
+                const int it = i * 4 * RT + kk;
+#pragma unroll
+                for (int f = EAN; f < NLD; ++f) {
+                  const int head = ((f - EAN + 1) * SP_BWD_DEN + SP_BWD_NUM - 1) / SP_BWD_NUM - 1;
+                  const int itf = f < NLD - SP_BWD_TAIL ? (head < NIT ? head : NIT - 1) : NIT - 1 - (NLD - 1 - f) / SP_BWD_TAILPER;
+                  if (itf == it) issue_row(f);
+                }
+                __builtin_amdgcn_sched_barrier(0);
               } else {
                 // iteration it of the wave's backward issues load it + EAN (the rest of the
                 // stream goes out in the first NLD - EAN iterations)
@@ -1105,12 +1171,13 @@ static void launch_split_g(const LTParams& P, const SplitWS& X, int grid, size_t
   // (fs_tuning.split_early: 0 = by shape, -1 = never)
   // Depth per width (profiles/r03/split_early_ab2.txt, launch ms): at G = 2 (128 KB of rows per
   // CU per step) 4 early loads are fastest (config 2: 0.300-0.302 vs 0.304-0.307 with 6), at
-  // G = 16 6 (config 5: 5.34-5.36 vs 5.58 with 4)
+  // G = 16 6 (config 5: 5.34-5.36 vs 5.58 with 4); depth 4 re-checked at G = 2 on the fenced
+  // schedule (round 8, SP_EG2: 6 / 8 / 2 early loads 278.6-280.1 / 275.4-276.7 / 278.1-280.5 us vs 265-268)
   // With a prox term (round 5) the anchor's slice (8 loads per wave) goes out ahead of the early
   // rows, and 2 early rows measured fastest (config 3, G = 4, launch us, profiles/r05/prox_early_depth.txt:
   // late 5,102-5,107; early 1: 4,678-4,691, 2: 4,488-4,530, 3: 4,605-4,622, 4: 4,539-4,544, 6: 4,699-4,715,
   // 8: 4,713-4,720)
-  constexpr int EARLY_G = (G == 2 && SP_EARLY > 4) ? 4 : SP_EARLY;
+  constexpr int EARLY_G = (G == 2 && SP_EARLY > SP_EG2) ? SP_EG2 : SP_EARLY;
 #ifndef SP_EP
 #define SP_EP 2
 #endif
