@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 19
+#define FS_ABI_VERSION 20
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -467,6 +467,20 @@ int fs_mix_solve_last_mode(void);
  * fs_mix_solve_blocked launch when it ran the qmc solver -- its workgroups K and clients per
  * lane (4 or 8; K = ceil(ldN / (16 * lane_clients))) -- else 0 and 0. */
 int fs_mix_solve_last_layout(int* workgroups, int* lane_clients);
+/* (ABI 20) host-only, no device state: what fs_mix_solve (blocks = 1) or fs_mix_solve_blocked
+ * (blocks > 1; its N % (4 blocks) check is not repeated here, and it launches only where the
+ * answer is qmc) would launch for this shape under the calling thread's tuning.
+ *   solver        FS_SOLVER_* as fs_mix_solve_last_mode reports it after the launch
+ *   workgroups, lane_clients   as fs_mix_solve_last_layout: qmc's K and clients per lane, else 0, 0
+ *   helpers       L2 prefetch helper workgroups, after the solver's own bound (given a workspace)
+ *   lead          steps they run ahead (0 without helpers)
+ *   poll_delay    qmc: s_sleep(1) units before a step's first poll, else 0
+ *   ws_bytes      workspace bytes the launch uses (<= fs_mix_solve_ws_bytes(N, C, Bv)) */
+typedef struct fs_mix_plan {
+  int solver, workgroups, lane_clients, helpers, lead, poll_delay;
+  int64_t ws_bytes;
+} fs_mix_plan;
+int fs_mix_solve_plan(int N, int C, int n_val, int epochs, int Bv, int blocks, fs_mix_plan* out);
 /* (ABI 15) Diagnostic (host state only): the kernel the calling thread's last fs_local_train
  * launched -- FS_LT_SINGLE (1, one workgroup per client), FS_LT_SPLIT (2), FS_LT_DBUF (3, the
  * split form's double-buffered instance: the rows streamed ahead of the hand-off),

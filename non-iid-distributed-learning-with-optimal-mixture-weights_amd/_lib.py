@@ -70,6 +70,7 @@ _SIGS = {
     'fs_mix_solve_blocked_covers': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'fs_mix_solve_last_mode': (C.c_int, []),
     'fs_mix_solve_last_layout': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'fs_mix_solve_plan': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'fs_feature_map': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     'fs_gram': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -92,7 +93,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
@@ -178,6 +179,21 @@ def last_mix_layout():
     k, nk = C.c_int(0), C.c_int(0)
     check(lib().fs_mix_solve_last_layout(C.byref(k), C.byref(nk)), 'fs_mix_solve_last_layout')
     return k.value, nk.value
+
+
+class MixPlan(C.Structure):
+    """fs_mix_plan (include/fedsim.h), field for field."""
+    _fields_ = [('solver', C.c_int), ('workgroups', C.c_int), ('lane_clients', C.c_int), ('helpers', C.c_int),
+                ('lead', C.c_int), ('poll_delay', C.c_int), ('ws_bytes', C.c_int64)]
+
+
+def mix_plan(N, C_, n_val, epochs, Bv, blocks=1):
+    """fs_mix_solve_plan as a dict: what fs_mix_solve (``blocks`` > 1: fs_mix_solve_blocked) would
+    launch for this shape under the calling thread's tuning -- host only, no GPU needed."""
+    out = MixPlan()
+    check(lib().fs_mix_solve_plan(int(N), int(C_), int(n_val), int(epochs), int(Bv), int(blocks), C.byref(out)),
+          'fs_mix_solve_plan')
+    return {k: getattr(out, k) for k, _ in MixPlan._fields_}
 
 
 def get_process_tuning():
@@ -272,12 +288,13 @@ def stream_ptr(stream=None):
 
 
 # the device sources each measured kernel is compiled from (its own file + the headers it includes;
-# local_train's planner and launch setup are host code, csrc/local_train_host.cpp, in no revision)
+# the planners and launch setups are host code, csrc/local_train_host.cpp and csrc/mixture_host.cpp,
+# in no revision)
 KERNEL_SOURCES = {
     'local_train': ('local_train.hip', 'local_train_split.hip', 'local_train_pair.hip', 'local_train_pipe.hip',
                     'local_train_dbuf.hip', 'split_common.h', 'local_train_forms.h', 'common.h',
                     'eval_rows.h', 'lanes.h'),
-    'mix_solve': ('mixture.hip', 'common.h', 'lanes.h'),
+    'mix_solve': ('mixture.hip', 'mixture_forms.h', 'common.h', 'lanes.h'),
     'mix_z': ('mix_z.hip', 'common.h'),
     'local_train_mse': ('local_train_mse.hip', 'mse_rows.h', 'common.h'),
     'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),

@@ -8,20 +8,13 @@
 //               the step): out = Z_b p, CE, grad_p = Z_b^T g, momentum update.
 #include "common.h"
 #include "lanes.h"
-
-#include <cstdlib>
+#include "mixture_forms.h"
 
 namespace fs {
-
-// client stride of a Z row segment: N rounded up to 4 (16-byte aligned class segments)
-__host__ __device__ __forceinline__ int mix_ldn(int N) { return (N + 3) & ~3; }
 
 // ----------------------------------------------------------------------------
 // p-solve: one workgroup of 1024 threads.  p and the momentum buffer live in LDS.
 // ----------------------------------------------------------------------------
-constexpr int MS_THREADS = 1024;
-constexpr int MS_WAVES = MS_THREADS / 64;
-constexpr int MS_MAXB = 64;
 
 __global__ __launch_bounds__(MS_THREADS) void mix_solve_kernel(const float* __restrict__ Z,
                                                               const int32_t* __restrict__ y,
@@ -111,8 +104,6 @@ __global__ __launch_bounds__(MS_THREADS) void mix_solve_kernel(const float* __re
 // buffer at its end, so Z streams from L2/MALL behind the arithmetic.  Two barriers per
 // step; a step costs ~1 us instead of three dependent global round trips.
 // ----------------------------------------------------------------------------
-constexpr int MS2_PER_THREAD = 4;     // float4 of staged rows per thread (one batch <= 64 KB)
-constexpr int MS2_NK = 4;             // clients per lane (N <= 256 on this path)
 
 template <int CMAX>
 __global__ __launch_bounds__(MS_THREADS) void mix_solve_staged_kernel(const float* __restrict__ Z,
@@ -364,8 +355,6 @@ __device__ __forceinline__ void swap_batch(float (&a)[M], float (&b)[M]) {
                    : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
   }
 }
-
-constexpr int MR_WAVES = 16;
 
 // Diagnostic build only (-DFS_MIX_STAMPS, `make stamps`): per-phase cycle sums of wave 0,
 // written after the solver's buf[N] as buf[N + 8 + 2k] (uint64); never in the shipped library.
@@ -633,38 +622,30 @@ __global__ __launch_bounds__(MR_WAVES * 64) void mix_solve_reg_kernel(const floa
   }
 }
 
-struct MixPrefetch {
-  unsigned* prog;   // progress word (null: no helpers)
-  int h, lead;      // helper workgroups, steps ahead
-};
+// clients per lane of the register solvers (mix_plan admits N <= 256 only)
+static int reg_nk(int N) { return N <= 64 ? 1 : (N <= 128 ? 2 : 4); }
 
 template <int NK, int CP, int CL>
-static void launch_mix_reg(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                           int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first,
-                           const MixPrefetch& pf) {
+static void launch_mix_reg_instance(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
   constexpr int depth = 3 * (CL + 2) <= 63 ? 3 : 2;   // CL + 2 loads per step stay in the vmcnt window
-  const int blocks = pf.prog ? 8 * std::min(pf.h, 31) + 1 : 1;
-  hipLaunchKernelGGL((mix_solve_reg_kernel<NK, CP, CL, depth>), dim3(blocks), dim3(MR_WAVES * 64), 0, st, Z, y,
-                     perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, pf.prog, std::min(pf.h, 31), pf.lead);
+  hipLaunchKernelGGL((mix_solve_reg_kernel<NK, CP, CL, depth>), dim3(8 * plan.helpers + 1), dim3(MR_WAVES * 64), 0, st,
+                     a.Z, a.y, a.perms, a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, a.prog,
+                     plan.helpers, plan.lead);
 }
 
-// register-resident solver for (N, C, Bv) if an instance covers it
-static bool mix_solve_reg(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                          int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first,
-                          const MixPrefetch& pf) {
-  if (Bv > MR_WAVES) return false;
-  const int nk = N <= 64 ? 1 : (N <= 128 ? 2 : (N <= 256 ? 4 : 0));
-#define MR_CASE(NK_, CP_, CL_)                                                                      \
-  if (nk == NK_ && C <= CL_) {                                                                      \
-    launch_mix_reg<NK_, CP_, CL_>(st, Z, y, perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, pf); \
-    return true;                                                                                    \
+int launch_mix_reg(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  const int nk = reg_nk(a.N);
+#define MR_CASE(NK_, CP_, CL_)                                        \
+  if (nk == NK_ && a.C <= CL_) {                                      \
+    launch_mix_reg_instance<NK_, CP_, CL_>(a, plan, st);              \
+    return FS_OK;                                                     \
   }
   // (the ring holds DEPTH * CL * NK floats per lane: larger shapes take the LDS-staged solver)
   MR_CASE(1, 2, 2) MR_CASE(1, 4, 4) MR_CASE(1, 8, 8) MR_CASE(1, 16, 10) MR_CASE(1, 16, 16) MR_CASE(1, 32, 24)
   MR_CASE(2, 2, 2) MR_CASE(2, 4, 4) MR_CASE(2, 8, 8) MR_CASE(2, 16, 10)
   MR_CASE(4, 2, 2) MR_CASE(4, 4, 4)
 #undef MR_CASE
-  return false;
+  return fail(FS_EUNSUPPORTED, "fs_mix_solve: no reg instance for this shape");
 }
 
 // ----------------------------------------------------------------------------
@@ -682,8 +663,6 @@ static bool mix_solve_reg(hipStream_t st, const float* Z, const int32_t* y, cons
 //     one v_permlane{32,16}_swap of (a, b) plus one add: after the swap every lane holds its
 //     own and its partner's copy of the element it keeps (SWAP = 0 keeps the select form).
 // ----------------------------------------------------------------------------
-constexpr int M2_WAVES = 8;
-
 // class_totals of lanes.h for two independent rows at once (the levels interleave)
 template <int CP>
 __device__ __forceinline__ void class_totals2(float (&v0)[CP], float (&v1)[CP], int lane, float& o0, float& o1) {
@@ -871,31 +850,24 @@ __global__ __launch_bounds__(M2_WAVES * 64) void mix_solve_reg2_kernel(const flo
 }
 
 template <int NK, int CP, int CL>
-static void launch_mix_reg2(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                            int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first,
-                            int z_bytes) {
+static void launch_mix_reg2_instance(const MixArgs& a, hipStream_t st) {
   constexpr int depth = 2 * CL * 3 <= 63 ? 3 : (2 * CL * 2 <= 63 ? 2 : 1);
-  hipLaunchKernelGGL((mix_solve_reg2_kernel<NK, CP, CL, depth>), dim3(1), dim3(M2_WAVES * 64), 0, st, Z, y,
-                     perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, z_bytes);
+  hipLaunchKernelGGL((mix_solve_reg2_kernel<NK, CP, CL, depth>), dim3(1), dim3(M2_WAVES * 64), 0, st, a.Z, a.y,
+                     a.perms, a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, mix_z_bytes(a));
 }
 
-// register-resident solver, form 2, for (N, C, Bv) if an instance covers it
-static bool mix_solve_reg2(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                           int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first) {
-  if (Bv > 2 * M2_WAVES || C > 10) return false;
-  const int64_t zb = (int64_t)nv * C * mix_ldn(N) * 4;
-  if (zb >= ((int64_t)1 << 31) || (int64_t)epochs * nv >= ((int64_t)1 << 31)) return false;   // 32-bit offsets
-  const int nk = N <= 64 ? 1 : (N <= 128 ? 2 : (N <= 256 ? 4 : 0));
-#define M2_CASE(NK_, CP_, CL_)                                                                              \
-  if (nk == NK_ && C <= CL_) {                                                                              \
-    launch_mix_reg2<NK_, CP_, CL_>(st, Z, y, perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, (int)zb);       \
-    return true;                                                                                            \
+int launch_mix_reg2(const MixArgs& a, const MixPlan&, hipStream_t st) {
+  const int nk = reg_nk(a.N);
+#define M2_CASE(NK_, CP_, CL_)                                        \
+  if (nk == NK_ && a.C <= CL_) {                                      \
+    launch_mix_reg2_instance<NK_, CP_, CL_>(a, st);                   \
+    return FS_OK;                                                     \
   }
   M2_CASE(1, 2, 2) M2_CASE(1, 4, 4) M2_CASE(1, 8, 8) M2_CASE(1, 16, 10)
   M2_CASE(2, 2, 2) M2_CASE(2, 4, 4) M2_CASE(2, 8, 8) M2_CASE(2, 16, 10)
   M2_CASE(4, 2, 2) M2_CASE(4, 4, 4)
 #undef M2_CASE
-  return false;
+  return fail(FS_EUNSUPPORTED, "fs_mix_solve: no reg2 instance for this shape");
 }
 
 // ----------------------------------------------------------------------------
@@ -923,7 +895,6 @@ static bool mix_solve_reg2(hipStream_t st, const float* Z, const int32_t* y, con
 //     DEPTH-deep register ring; row indices and labels per lane, DEPTH steps ahead.
 // Optional L2 prefetch helpers as for the register solver (FS_MIX_PF_H).
 // ----------------------------------------------------------------------------
-constexpr int MQ_WAVES = 4;
 // Diagnostic build only (`make probe`, -DFS_MIX_PROBE_NOLOAD): the quarter-wave solver skips
 // its in-loop Z loads (the ring keeps its first rows: wrong p, timing only) -- what a step costs
 // without the vector-memory issue.  Never in the shipped library.
@@ -1437,57 +1408,41 @@ __global__ __launch_bounds__(2 * MQ_WAVES * 64) void mix_solve_quadl_kernel(
 }
 
 template <int NK, int CL, int SPL = quad_split<CL>()>
-static void launch_mix_quad(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                            int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first,
-                            int z_bytes, const MixPrefetch& pf) {
+static void launch_mix_quad_instance(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
   // ring: DEPTH x CL x NK floats per lane (<= 160), CL*NK/4 + 2 loads per step in the vmcnt window
   constexpr int depth = (3 * CL * NK <= 160 && 3 * (CL * NK / 4 + 2) <= 63) ? 3 : 2;
-  const int blocks = pf.prog ? 8 * std::min(pf.h, 31) + 1 : 1;   // helpers: the solver's XCD only
-  // softmax on v_exp_f32 / v_rcp_f32 (e / sum) by default: config 2 1.28-1.29 -> 1.21-1.23 us per
-  // step (r02s2fx), within the fp32 tolerance of the oracle like every other solver;
-  // fs_tuning.mix_exact_softmax: torch's exp(o - m - log(sum)) form with libm expf / logf
-  // loader waves (mix_solve_quadl_kernel): config 2's instance (NK = 8, CL = 10) by default,
-  // fs_tuning.mix_quad_loaders = -1 off
-  // (2 classes in the register ring, 8 through the LDS ring: 0.837-0.839 us per step against
-  // 0.851-0.856 with 3 and 0.851-0.874 with 1, profiles/r04/quad_loader_split.txt)
+  const dim3 grid(8 * plan.helpers + 1);   // helpers: the solver's XCD only
+  const int zb = mix_z_bytes(a);
+  // the loader-wave kernel exists for config 2's instance (NK = 8, CL = 10) only
   if constexpr (NK == 8 && CL == 10 && SPL < CL) {
-    if (!tuning().mix_exact_softmax && tuning().mix_quad_loaders >= 0) {
-      hipLaunchKernelGGL((mix_solve_quadl_kernel<NK, CL, 2>), dim3(blocks), dim3(2 * MQ_WAVES * 64), 0, st, Z, y,
-                         perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, z_bytes, pf.prog, std::min(pf.h, 31),
-                         pf.lead);
+    if (plan.loaders) {
+      hipLaunchKernelGGL((mix_solve_quadl_kernel<NK, CL, 2>), grid, dim3(2 * MQ_WAVES * 64), 0, st, a.Z, a.y, a.perms,
+                         a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, zb, a.prog, plan.helpers,
+                         plan.lead);
       return;
     }
   }
-  if (!tuning().mix_exact_softmax)
-    hipLaunchKernelGGL((mix_solve_quad_kernel<NK, CL, depth, SPL, true>), dim3(blocks), dim3(MQ_WAVES * 64), 0, st, Z,
-                       y, perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, z_bytes, pf.prog, std::min(pf.h, 31),
-                       pf.lead);
+  if (plan.fast_softmax)
+    hipLaunchKernelGGL((mix_solve_quad_kernel<NK, CL, depth, SPL, true>), grid, dim3(MQ_WAVES * 64), 0, st, a.Z, a.y,
+                       a.perms, a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, zb, a.prog,
+                       plan.helpers, plan.lead);
   else
-    hipLaunchKernelGGL((mix_solve_quad_kernel<NK, CL, depth, SPL, false>), dim3(blocks), dim3(MQ_WAVES * 64), 0, st, Z,
-                       y, perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, z_bytes, pf.prog, std::min(pf.h, 31),
-                       pf.lead);
+    hipLaunchKernelGGL((mix_solve_quad_kernel<NK, CL, depth, SPL, false>), grid, dim3(MQ_WAVES * 64), 0, st, a.Z, a.y,
+                       a.perms, a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, zb, a.prog,
+                       plan.helpers, plan.lead);
 }
 
-static bool quad_covers(int N, int C, int Bv, int nv, int epochs) {
-  const int64_t zb = (int64_t)nv * C * mix_ldn(N) * 4;
-  return Bv <= 16 && (N <= 64 ? C <= 16 : (N <= 128 && C <= 10)) && zb < ((int64_t)1 << 31) && (int64_t)epochs * nv < ((int64_t)1 << 31);
-}
-
-static bool mix_solve_quad(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C,
-                           int nv, int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first,
-                           const MixPrefetch& pf) {
-  if (!quad_covers(N, C, Bv, nv, epochs)) return false;
-  const int zb = (int)((int64_t)nv * C * mix_ldn(N) * 4);
-  const int nk = N <= 64 ? 4 : 8;
-#define MQ_CASE(NK_, CL_)                                                                                    \
-  if (nk == NK_ && C <= CL_) {                                                                               \
-    launch_mix_quad<NK_, CL_>(st, Z, y, perms, N, C, nv, epochs, Bv, lr, mom, p, buf, first, zb, pf);         \
-    return true;                                                                                             \
+int launch_mix_quad(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  const int nk = a.N <= 64 ? 4 : 8;
+#define MQ_CASE(NK_, CL_)                                             \
+  if (nk == NK_ && a.C <= CL_) {                                      \
+    launch_mix_quad_instance<NK_, CL_>(a, plan, st);                  \
+    return FS_OK;                                                     \
   }
   MQ_CASE(4, 2) MQ_CASE(4, 4) MQ_CASE(4, 8) MQ_CASE(4, 10) MQ_CASE(4, 16)
   MQ_CASE(8, 2) MQ_CASE(8, 4) MQ_CASE(8, 8) MQ_CASE(8, 10)
 #undef MQ_CASE
-  return false;
+  return fail(FS_EUNSUPPORTED, "fs_mix_solve: no quad instance for this shape");
 }
 
 // ----------------------------------------------------------------------------
@@ -1769,11 +1724,6 @@ __global__ __launch_bounds__(64) void mix_solve_bin_kernel(const float* __restri
   if (lane == 0 && total > 0) *first_flag = 0;
 }
 
-static bool bin_covers(int N, int C, int Bv, int nv, int epochs) {
-  const int64_t zb = (int64_t)nv * C * mix_ldn(N) * 4;
-  return N <= 16 && C <= 2 && Bv <= 16 && zb < ((int64_t)1 << 31) && (int64_t)epochs * nv < ((int64_t)1 << 31);
-}
-
 // ----------------------------------------------------------------------------
 // p-solve, multi-CU form (Bv <= 16, C <= 16, N <= 2048).  One workgroup on one CU cannot
 // stream a batch of Z rows faster than ~33 GB/s (gathered rows from the Infinity Cache,
@@ -1798,12 +1748,6 @@ static bool bin_covers(int N, int C, int Bv, int nv, int epochs) {
 // zeroed before each launch; tags are step + 1.  Every spin is bounded: a timeout sets the
 // error word and poisons p with NaN (the kernel still drains).
 // ----------------------------------------------------------------------------
-constexpr int MC_THREADS = 256;
-constexpr int MC_XCDS = 8;
-constexpr int MC_KMAX = 32;
-constexpr int MC_SLOT = 256;                     // granules per workgroup per parity
-constexpr int MC_TOT = 256;                      // hop-2 granules (logit totals) per parity
-constexpr unsigned MC_SPIN_LIMIT = 1u << 20;
 
 // spin on one granule until it carries `tag`; false (and the error word set) on a timeout
 __device__ __forceinline__ bool mc_wait(const unsigned long long* g, unsigned tag, unsigned long long& out,
@@ -2027,62 +1971,18 @@ __global__ __launch_bounds__(MC_THREADS) void mix_solve_mc_kernel(const float* _
   if (k == 0 && t == 0 && total > 0) *first_flag = 0;
 }
 
-// caller-owned workspace of the multi-CU solver: [2][K][MC_SLOT] exchange granules (zeroed
-// before every launch) followed by a 256-byte error block (sticky: only the caller clears it)
-constexpr int64_t MC_ERR_BYTES = 256;
-
-static int64_t mc_xbytes(int K) { return (int64_t)sizeof(unsigned long long) * 2 * (K * MC_SLOT + MC_TOT); }
-
-// exchange form: two hops, except at S = 8 (one) -- r02n, N = 100, C = 10, us per step, one hop /
-// two hops (Z issued after the exchange): S = 64 (K = 2) 5.50 / 4.14, S = 32 (K = 4) 4.43 / 2.90,
-// S = 16 (K = 7) 3.95 / 2.87, S = 8 (K = 13) 3.25 / 3.79
-static int mc_hops(int K, int S) { return (K >= 2 && S >= 16) ? 2 : 1; }
-
-// the exchange kernels' spin bound (fs_tuning.spin_limit) and the injected-timeout test knob
-// (the kernels report a timeout at the first exchange when the bound they get is 0)
-static unsigned mc_spin_limit() {
-  const fs_tuning t = tuning();
-  if (t.inject_timeout) return 0u;
-  return t.spin_limit ? t.spin_limit : MC_SPIN_LIMIT;
-}
-
-// slice width for N clients (0: not covered): S clients per workgroup, K = ceil(ldN / S) <= 32
-static int mc_slice(int N) {
-  const int ldN = mix_ldn(N);
-  for (int s : {8, 16, 32, 64})
-    if ((ldN + s - 1) / s <= MC_KMAX && (s > 8 || ldN <= 128)) return s;
-  return 0;
-}
-
-static bool mc_covers(int N, int C, int Bv) { return mc_slice(N) != 0 && C <= 16 && Bv <= 16; }
-
-static int mix_solve_mc(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C, int nv,
-                        int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first, void* d_ws,
-                        int64_t ws_bytes, MixPrefetch pf) {
-  if (!mc_covers(N, C, Bv)) return 1;            // not covered
-  const int S = mc_slice(N);
-  const int K = (mix_ldn(N) + S - 1) / S;
-  const int64_t xbytes = mc_xbytes(K);
-  if (!d_ws || ws_bytes < xbytes + MC_ERR_BYTES)
-    return fail(FS_EINVAL, "fs_mix_solve: workspace too small (see fs_mix_solve_ws_bytes)");
-  unsigned long long* ws = reinterpret_cast<unsigned long long*>(d_ws);
-  unsigned* err = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_ws) + ws_bytes - MC_ERR_BYTES);
-  hipError_t e = hipMemsetAsync(ws, 0, (size_t)xbytes, st);
-  if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
-  const unsigned spin_limit = mc_spin_limit();
-  const dim3 grid(MC_XCDS * K), block(MC_THREADS);
-  const int hops = mc_hops(K, S);
-  // the next Z slice is issued after the exchange -- r02i, us per step, (hops, issued at the top /
-  // after hop 1 / after the exchange): N = 1000, C = 10, K = 32: (1, top) 6.61, (2, top) 6.03,
-  // (2, hop 1) 5.45, (2, exchange) 5.44; N = 300, C = 4, K = 19: 4.33 / 4.34 / 4.08 / 3.38
-  if (pf.prog) pf.h = std::min(pf.h, (MC_XCDS - 1) * K);   // helpers: the grid's other-XCD blocks
-#define MC_CASE(S_, H_)                                                                                       \
-  if (S == S_ && hops == H_)                                                                                  \
-    hipLaunchKernelGGL((mix_solve_mc_kernel<S_, H_>), grid, block, 0, st, Z, y, perms, N, C, nv, epochs, Bv, lr,  \
-                       mom, p, buf, first, ws, err, K, spin_limit, pf.prog, pf.h, pf.lead);
+int launch_mix_mc(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  const dim3 grid(MC_XCDS * plan.K), block(MC_THREADS);   // helpers: the grid's other-XCD blocks
+#define MC_CASE(S_, H_)                                                                                          \
+  if (plan.S == S_ && plan.hops == H_) {                                                                         \
+    hipLaunchKernelGGL((mix_solve_mc_kernel<S_, H_>), grid, block, 0, st, a.Z, a.y, a.perms, a.N, a.C, a.nv,     \
+                       a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, a.xbuf, a.err, plan.K, plan.spin_limit, \
+                       a.prog, plan.helpers, plan.lead);                                                         \
+    return FS_OK;                                                                                                \
+  }
   MC_CASE(8, 1) MC_CASE(16, 2) MC_CASE(32, 2) MC_CASE(64, 2)
 #undef MC_CASE
-  return 0;
+  return fail(FS_EUNSUPPORTED, "fs_mix_solve: no mc instance for this slice");
 }
 
 // ----------------------------------------------------------------------------
@@ -2098,8 +1998,6 @@ static int mix_solve_mc(hipStream_t st, const float* Z, const int32_t* y, const 
 // ahead).  Spins are bounded; a timeout sets the error
 // word and poisons p with NaN.
 // ----------------------------------------------------------------------------
-constexpr int QMC_KMAX = 16;
-
 template <int NK, int CL, int DEPTH, int SPL>
 __global__ __launch_bounds__(MQ_WAVES * 64) void mix_solve_qmc_kernel(
     const float* __restrict__ Z, const int32_t* __restrict__ y, const int32_t* __restrict__ perms, int N, int C,
@@ -2362,285 +2260,58 @@ __global__ __launch_bounds__(MQ_WAVES * 64) void mix_solve_qmc_kernel(
   }
 }
 
-// clients per lane: 4 (64 per workgroup) wherever K = ceil(N / 64) <= 16 workgroups, else 8
-// (C <= 10 only).  Round 4 (profiles/r04/qmc_lane_ab*.txt, us per step, 8 vs 4): N = 1000
-// C = 10 3.60-3.71 vs 3.30; N = 300 3.00 vs 2.50; N = 520 3.23 vs 2.73 -- half the gather per CU
-// outweighs the hop's 16 partners since the hop re-polls all missing partners at once (round 2,
-// polling them one after another, measured the two the same).  fs_tuning.mix_qmc_lane_clients
-// forces one.
-static int qmc_nk(int N, int C) {
-  const int f = tuning().mix_qmc_lane_clients;
-  if (C > 10 || f == 4) return 4;
-  if (f == 8) return 8;
-  return (mix_ldn(N) + 63) / 64 <= QMC_KMAX ? 4 : 8;
+int launch_mix_qmc(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  const dim3 grid(MC_XCDS * (plan.K + plan.helpers)), block(MQ_WAVES * 64);
+  const int zb = mix_z_bytes(a), zL = mix_ldn(a.N) / plan.zR;
+#define QMC_CASE(NK_, CL_, DEPTH_)                                                                              \
+  hipLaunchKernelGGL((mix_solve_qmc_kernel<NK_, CL_, DEPTH_, quad_split<CL_>()>), grid, block, 0, st, a.Z, a.y, \
+                     a.perms, a.N, a.C, a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, zb, a.xbuf,     \
+                     a.err, plan.K, plan.spin_limit, a.prog, plan.helpers, plan.lead, zL, plan.zR,              \
+                     plan.poll_delay)
+  if (plan.nk == 8) QMC_CASE(8, 10, 2);
+  else if (a.C <= 10) QMC_CASE(4, 10, 3);
+  else QMC_CASE(4, 16, 2);
+#undef QMC_CASE
+  return FS_OK;
 }
 
-// s_sleep(1) units before a step's first poll (fs_tuning.mix_poll_delay: 0 = by shape, -1 =
-// none, n > 0 = n).  By shape from the sweeps (profiles/r04/qmc_poll_delay*.txt, us per step,
-// none / best, at helper lead 6): N = 1000, C = 10 (K = 16) 3.24 / 2.73 at 14 (12-16 within 1 %);
-// N = 1000, C = 4 2.86 / 2.28 at 8 (2.49 at 16); N = 300 2.41 / 1.95 at 8; N = 520 2.68 / 2.07 at 8.
-// At lead 8 (the qmc default since) the K = 16 optimum moved to 10: 2.48 vs 2.58 us at 14
-// (profiles/r04/qmc_delay_lead_grid.txt).
-static int qmc_poll_delay(int K, int C) {
-  const int t = tuning().mix_poll_delay;
-  if (t < 0) return 0;
-  if (t > 0) return t;
-  return (K >= 12 && C >= 8) ? 10 : 8;
+// ---- the one-workgroup solvers without an instance table ----
+
+// dynamic LDS beyond the 64 KB a kernel gets unasked
+static int mix_lds_attr(const void* kfn, size_t lds) {
+  if (lds <= 64 * 1024) return FS_OK;
+  hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  return e == hipSuccess ? FS_OK : fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
 }
 
-static bool qmc_covers(int N, int C, int Bv, int nv, int epochs) {
-  const int64_t zb = (int64_t)nv * C * mix_ldn(N) * 4;
-  const int nk = qmc_nk(N, C);
-  return Bv <= 16 && N > 128 && C <= 16 && (mix_ldn(N) + 16 * nk - 1) / (16 * nk) <= QMC_KMAX &&
-         zb < ((int64_t)1 << 31) && (int64_t)epochs * nv < ((int64_t)1 << 31);
+int launch_mix_staged(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  if (int rc = mix_lds_attr(reinterpret_cast<const void*>(&mix_solve_staged_kernel<16>), plan.lds)) return rc;
+  hipLaunchKernelGGL(mix_solve_staged_kernel<16>, dim3(1), dim3(MS_THREADS), plan.lds, st, a.Z, a.y, a.perms, a.N, a.C,
+                     a.nv, a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first);
+  return FS_OK;
 }
 
-// the calling thread's last multi-CU launch layout (fs_mix_solve_last_layout): workgroups K and
-// clients per lane NK of the qmc solver (0, 0 after any other solver)
-static thread_local int t_last_k = 0, t_last_nk = 0;
+int launch_mix_global(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  if (int rc = mix_lds_attr(reinterpret_cast<const void*>(&mix_solve_kernel), plan.lds)) return rc;
+  hipLaunchKernelGGL(mix_solve_kernel, dim3(1), dim3(MS_THREADS), plan.lds, st, a.Z, a.y, a.perms, a.N, a.C, a.nv,
+                     a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first);
+  return FS_OK;
+}
 
-// 1: not covered; 0: launched; < 0: error
-static int mix_solve_qmc(hipStream_t st, const float* Z, const int32_t* y, const int32_t* perms, int N, int C, int nv,
-                         int epochs, int Bv, float lr, float mom, float* p, float* buf, int* first, void* d_ws,
-                         int64_t ws_bytes, MixPrefetch pf, int zR = 1) {
-  if (!qmc_covers(N, C, Bv, nv, epochs)) return 1;
-  const int zL = mix_ldn(N) / zR;
-  const int nk = qmc_nk(N, C);
-  const int K = (mix_ldn(N) + 16 * nk - 1) / (16 * nk);
-  const int64_t xbytes = mc_xbytes(K);
-  if (!d_ws || ws_bytes < xbytes + MC_ERR_BYTES)
-    return fail(FS_EINVAL, "fs_mix_solve: workspace too small (see fs_mix_solve_ws_bytes)");
-  unsigned long long* ws = reinterpret_cast<unsigned long long*>(d_ws);
-  unsigned* err = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_ws) + ws_bytes - MC_ERR_BYTES);
-  hipError_t e = hipMemsetAsync(ws, 0, (size_t)xbytes, st);
-  if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
-  const unsigned spin_limit = mc_spin_limit();
-  const int h = pf.prog ? std::min(pf.h, 32 - K) : 0;   // the solvers' XCD has 32 CUs
-  const dim3 grid(MC_XCDS * (K + h)), block(MQ_WAVES * 64);
-  const int zb = (int)((int64_t)nv * C * mix_ldn(N) * 4);
-  const int pd = qmc_poll_delay(K, C);
-  t_last_k = K;
-  t_last_nk = nk;
-  if (nk == 8)
-    hipLaunchKernelGGL((mix_solve_qmc_kernel<8, 10, 2, quad_split<10>()>), grid, block, 0, st, Z, y, perms, N, C, nv,
-                       epochs, Bv, lr, mom, p, buf, first, zb, ws, err, K, spin_limit, pf.prog, h, pf.lead, zL, zR,
-                       pd);
-  else if (C <= 10)
-    hipLaunchKernelGGL((mix_solve_qmc_kernel<4, 10, 3, quad_split<10>()>), grid, block, 0, st, Z, y, perms, N, C, nv,
-                       epochs, Bv, lr, mom, p, buf, first, zb, ws, err, K, spin_limit, pf.prog, h, pf.lead, zL, zR,
-                       pd);
+int launch_mix_wave(const MixArgs& a, const MixPlan&, hipStream_t st) {
+  hipLaunchKernelGGL(mix_solve_wave_kernel, dim3(1), dim3(64), 0, st, a.Z, a.y, a.perms, a.N, a.C, a.nv, a.epochs,
+                     a.Bv, a.lr, a.mom, a.p, a.buf, a.first);
+  return FS_OK;
+}
+
+int launch_mix_bin(const MixArgs& a, const MixPlan& plan, hipStream_t st) {
+  if (plan.fast_softmax)
+    hipLaunchKernelGGL(mix_solve_bin_kernel<true>, dim3(1), dim3(64), 0, st, a.Z, a.y, a.perms, a.N, a.C, a.nv,
+                       a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, mix_z_bytes(a));
   else
-    hipLaunchKernelGGL((mix_solve_qmc_kernel<4, 16, 2, quad_split<16>()>), grid, block, 0, st, Z, y, perms, N, C, nv,
-                       epochs, Bv, lr, mom, p, buf, first, zb, ws, err, K, spin_limit, pf.prog, h, pf.lead, zL, zR,
-                       pd);
-  return 0;
+    hipLaunchKernelGGL(mix_solve_bin_kernel<false>, dim3(1), dim3(64), 0, st, a.Z, a.y, a.perms, a.N, a.C, a.nv,
+                       a.epochs, a.Bv, a.lr, a.mom, a.p, a.buf, a.first, mix_z_bytes(a));
+  return FS_OK;
 }
 
 }  // namespace fs
-
-using namespace fs;
-
-static thread_local int t_last_solver = 0;
-
-extern "C" int fs_mix_solve_last_mode(void) { return t_last_solver; }
-
-extern "C" int fs_mix_solve_last_layout(int* workgroups, int* lane_clients) {
-  FS_REQUIRE(workgroups && lane_clients, "null pointer");
-  const bool q = t_last_solver == FS_SOLVER_QMC;
-  *workgroups = q ? fs::t_last_k : 0;
-  *lane_clients = q ? fs::t_last_nk : 0;
-  return FS_OK;
-}
-
-extern "C" int64_t fs_mix_solve_ws_bytes(int N, int C, int Bv) {
-  if (N < 1) return MC_ERR_BYTES;
-  const int S = mc_slice(N);
-  const int K = S ? (mix_ldn(N) + S - 1) / S : 0;
-  const int64_t mc = mc_covers(N, C, Bv) ? mc_xbytes(K) : 0;
-  const int64_t qmc = mc_xbytes((mix_ldn(N) + 63) / 64);   // the larger K of either lane width
-  return std::max(mc, (N > 128 && C <= 16 && Bv <= 16) ? qmc : (int64_t)0) + MC_ERR_BYTES;
-}
-
-// L2 prefetch helper setup of fs_mix_solve / fs_mix_solve_blocked (0, or an error status)
-static int mix_prefetch_setup(const fs_tuning& tune, bool use_quad, bool use_qmc, int N, int C, int n_val, void* d_ws,
-                              int64_t ws_bytes, hipStream_t st0, MixPrefetch& pf) {
-  // L2 prefetch helpers (fs_tuning.mix_prefetch: 0 = by solver, -1 = none, n): 4 for the
-  // quarter-wave solver, whose gather they speed up (r02s2k, 1.42-1.47 -> 1.35-1.43 us per step
-  // at config 2), 16 for qmc, none for the others, where they measured nothing; they run
-  // mix_prefetch_lead (0: 16) steps ahead; the progress word lives in the error block (byte 128)
-  // (quad: only when Z outgrows the L2s -- at config 1's 0.6 MB the helpers cost 3 %, r02s2c1)
-  const bool z_big = (int64_t)n_val * C * mix_ldn(N) * 4 > ((int64_t)16 << 20);
-  const int h = tune.mix_prefetch > 0 ? tune.mix_prefetch
-                : (tune.mix_prefetch < 0 ? 0 : ((use_quad && z_big) ? 4 : (use_qmc ? 24 : 0)));
-  // default lead: 16 steps for the quarter-wave solver; 8 for qmc, whose helpers (round 4:
-  // LDS-DMA pieces, the solver's progress published every step) keep a few steps of rows in
-  // the XCD's 4 MB L2 ahead of the solver -- at config 5 before the first-poll delay, 24
-  // helpers, leads 4 / 6 / 8 / 12: 3.85 / 3.62 / 3.76 / 3.81 us per step, none: 4.40
-  // (profiles/r04/mix_solve_helper_sweep.txt); with it (16 helpers at K = 16), leads 6 / 8 / 10
-  // / 12 / 16: 2.70-2.72 / 2.58 / 2.62-2.63 / 2.65 / 2.66, and at N = 300 1.96 for 6 and 8
-  // (profiles/r04/qmc_lead_sweep.txt); at N = 800 (K = 13) 8 is faster (2.33 vs 2.38-2.40), at
-  // N = 520 (K = 9) 6 (2.08 vs 2.18-2.24, profiles/r04/qmc_lead_sweep2.txt): 8 from K = 12, as
-  // the first-poll delay's step (qmc_poll_delay)
-  int qmc_k = 0;
-  if (use_qmc) {
-    const int lw = 16 * qmc_nk(N, C);
-    qmc_k = (mix_ldn(N) + lw - 1) / lw;
-  }
-  const int lead = tune.mix_prefetch_lead > 0 ? tune.mix_prefetch_lead : (use_qmc ? (qmc_k >= 12 ? 8 : 6) : 16);
-  if (h > 0 && d_ws && ws_bytes >= MC_ERR_BYTES) {
-    pf.prog = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d_ws) + ws_bytes - MC_ERR_BYTES + 128);
-    pf.h = h;
-    pf.lead = lead;
-    hipError_t e = hipMemsetAsync(pf.prog, 0, sizeof(unsigned), st0);
-    if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
-  }
-  return 0;
-}
-
-extern "C" int fs_mix_solve(const float* d_Z, const int32_t* d_labels, const int32_t* d_perms, int N, int C,
-                            int n_val, int epochs, int Bv, float lr_p, float momentum, float* d_p, float* d_buf,
-                            int* d_first, void* d_ws, int64_t ws_bytes, void* stream) {
-  FS_REQUIRE(N >= 1 && C >= 1 && n_val >= 1 && epochs >= 0, "bad sizes");
-  FS_REQUIRE(Bv >= 1 && Bv <= MS_MAXB, "valid batch size must be in [1, 64]");
-  FS_REQUIRE(d_Z && d_labels && d_perms && d_p && d_buf && d_first, "null pointer");
-  hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
-  // solver choice: by shape, or forced by fs_tuning.mix_solver (tests, diagnostics; a forced
-  // solver that does not cover the shape falls through to the next one)
-  const fs_tuning tune = tuning();
-  const int want = tune.mix_solver;
-  const bool aut = want == FS_SOLVER_AUTO;
-  // two classes, N <= 16 (config 1): the one-wave binary solver; one wave where it measured
-  // fastest (N <= 16, C = 3..4: 0.616 vs 0.62 us per step); else the quarter-wave solver
-  const bool auto_wave = N <= 16 && C >= 3 && C <= 4 && Bv <= 16;
-  const bool use_quad = (aut && !auto_wave && quad_covers(N, C, Bv, n_val, epochs)) || want == FS_SOLVER_QUAD;
-  // the multi-CU quarter-wave solver where the single-workgroup register solvers end (N > 256)
-  const bool use_qmc = want == FS_SOLVER_QMC || (aut && N > 256 && qmc_covers(N, C, Bv, n_val, epochs));
-  MixPrefetch pf{nullptr, 0, 0};
-  if (int rc = mix_prefetch_setup(tune, use_quad, use_qmc, N, C, n_val, d_ws, ws_bytes, st0, pf)) return rc;
-  // by shape: one wave for N <= 16, C <= 4; the quarter-wave solver (+ L2 prefetch helpers) for
-  // N <= 64, C <= 16 or N <= 128, C <= 10; the register solvers where an instance covers the
-  // shape (no cross-CU exchange: ~1-2.5 us per step); for N > 256 the multi-CU quarter-wave
-  // solver (one exchange hop per step; 3.9 us at N = 1000, C = 10) where it covers, else the
-  // multi-CU solver (two hops, ~4-7 us per step, 7-11x the single-workgroup staged / global
-  // solvers at N = 200..1000, C = 10); else those.
-  if (((aut && N <= 16 && C <= 2) || want == FS_SOLVER_BIN) && bin_covers(N, C, Bv, n_val, epochs)) {
-    const int zb = (int)((int64_t)n_val * C * mix_ldn(N) * 4);
-    if (!tune.mix_exact_softmax)
-      hipLaunchKernelGGL(mix_solve_bin_kernel<true>, dim3(1), dim3(64), 0, st0, d_Z, d_labels, d_perms, N, C, n_val,
-                         epochs, Bv, lr_p, momentum, d_p, d_buf, d_first, zb);
-    else
-      hipLaunchKernelGGL(mix_solve_bin_kernel<false>, dim3(1), dim3(64), 0, st0, d_Z, d_labels, d_perms, N, C, n_val,
-                         epochs, Bv, lr_p, momentum, d_p, d_buf, d_first, zb);
-    t_last_solver = FS_SOLVER_BIN;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  if (((aut && auto_wave) || want == FS_SOLVER_WAVE) && N <= 16 && C <= 4 && Bv <= 16) {
-    hipLaunchKernelGGL(mix_solve_wave_kernel, dim3(1), dim3(64), 0, st0, d_Z, d_labels, d_perms, N, C, n_val, epochs,
-                       Bv, lr_p, momentum, d_p, d_buf, d_first);
-    t_last_solver = 6;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  if (use_quad &&
-      mix_solve_quad(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf, d_first, pf)) {
-    t_last_solver = 8;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  // form 2 (two rows per wave) where it measured faster: N in (128, 256], NK = 4 (2.0 vs 4.1 us
-  // per step at N = 256, C = 4); below that the one-row form is as fast or faster (r02g)
-  if (((aut && N > 128) || want == FS_SOLVER_REG2) &&
-      mix_solve_reg2(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf, d_first)) {
-    t_last_solver = 5;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  if ((aut || want == FS_SOLVER_REG) &&
-      mix_solve_reg(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf, d_first,
-                    pf)) {
-    t_last_solver = 1;
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  if (use_qmc) {
-    const int rc = mix_solve_qmc(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf,
-                                 d_first, d_ws, ws_bytes, pf);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      t_last_solver = 9;
-      FS_LAUNCH_CHECK();
-      return FS_OK;
-    }
-  }
-  if (aut || want == FS_SOLVER_MC) {
-    const int rc = mix_solve_mc(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf,
-                                d_first, d_ws, ws_bytes, pf);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      t_last_solver = 2;
-      FS_LAUNCH_CHECK();
-      return FS_OK;
-    }
-  }
-  {
-    // LDS-staged solver: two batches of Z rows + p, buf and the wave partials must fit
-    const int CN4 = C * mix_ldn(N);
-    const size_t lds2 = sizeof(float) * (2 * (size_t)Bv * CN4 + 2 * (size_t)N + (size_t)MS_WAVES * N);
-    if (want != FS_SOLVER_GLOBAL && N <= 64 * MS2_NK && C <= 16 && lds2 <= 150 * 1024 && (size_t)Bv * (CN4 / 4) <= (size_t)MS_THREADS * MS2_PER_THREAD) {
-      const void* kfn = reinterpret_cast<const void*>(&mix_solve_staged_kernel<16>);
-      if (lds2 > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
-      }
-      hipLaunchKernelGGL(mix_solve_staged_kernel<16>, dim3(1), dim3(MS_THREADS), lds2, st0, d_Z, d_labels, d_perms, N,
-                         C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf, d_first);
-      t_last_solver = 3;
-      FS_LAUNCH_CHECK();
-      return FS_OK;
-    }
-  }
-  const size_t lds = sizeof(float) * (2 * (size_t)N + 2 * MS_MAXB * (size_t)C) + sizeof(int) * 2 * MS_MAXB;
-  FS_REQUIRE(lds <= 160 * 1024, "N too large for the LDS-resident mixture solve");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mix_solve_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(FS_EHIP, std::string("fs_mix_solve: ") + hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(mix_solve_kernel, dim3(1), dim3(MS_THREADS), lds, st, d_Z, d_labels, d_perms, N, C, n_val,
-                     epochs, Bv, lr_p, momentum, d_p, d_buf, d_first);
-  t_last_solver = 4;
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-extern "C" int fs_mix_solve_blocked_covers(int N, int C, int n_val, int epochs, int Bv) {
-  const fs_tuning tune = tuning();
-  const bool forced_other = tune.mix_solver != FS_SOLVER_AUTO && tune.mix_solver != FS_SOLVER_QMC;
-  return !forced_other && N >= 1 && C >= 1 && n_val >= 1 && epochs >= 0 && qmc_covers(N, C, Bv, n_val, epochs) &&
-         (tune.mix_solver == FS_SOLVER_QMC || N > 256);
-}
-
-extern "C" int fs_mix_solve_blocked(const float* d_Z, int blocks, const int32_t* d_labels, const int32_t* d_perms,
-                                    int N, int C, int n_val, int epochs, int Bv, float lr_p, float momentum, float* d_p,
-                                    float* d_buf, int* d_first, void* d_ws, int64_t ws_bytes, void* stream) {
-  FS_REQUIRE(N >= 1 && C >= 1 && n_val >= 1 && epochs >= 0, "bad sizes");
-  FS_REQUIRE(blocks >= 1 && N % (4 * blocks) == 0, "N must be a multiple of 4 * blocks");
-  FS_REQUIRE(Bv >= 1 && Bv <= MS_MAXB, "valid batch size must be in [1, 64]");
-  FS_REQUIRE(d_Z && d_labels && d_perms && d_p && d_buf && d_first, "null pointer");
-  hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
-  const fs_tuning tune = tuning();
-  if (!fs_mix_solve_blocked_covers(N, C, n_val, epochs, Bv))
-    return fail(FS_EUNSUPPORTED, "fs_mix_solve_blocked: the rank-blocked Z layout is read by the qmc solver only "
-                                 "(N > 256, C <= 16, Bv <= 16); use fs_mix_solve on the standard layout");
-  MixPrefetch pf{nullptr, 0, 0};
-  if (int rc = mix_prefetch_setup(tune, false, true, N, C, n_val, d_ws, ws_bytes, st0, pf)) return rc;
-  const int rc = mix_solve_qmc(st0, d_Z, d_labels, d_perms, N, C, n_val, epochs, Bv, lr_p, momentum, d_p, d_buf,
-                               d_first, d_ws, ws_bytes, pf, blocks);
-  if (rc < 0) return rc;
-  if (rc != 0) return fail(FS_EUNSUPPORTED, "fs_mix_solve_blocked: shape not covered");
-  t_last_solver = FS_SOLVER_QMC;
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
