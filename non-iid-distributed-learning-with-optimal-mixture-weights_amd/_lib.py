@@ -166,6 +166,24 @@ def lib():
     return _lib
 
 
+_randperm_capped = None
+
+
+def randperm_device_capped():
+    """fs::randperm_device (csrc/randperm_geom.h), the internal entry the round plan calls:
+    fs_randperm_device's arguments with ``max_blocks`` before the stream (> 0: the capped,
+    persistent geometry).  No part of the C ABI -- a C++ symbol of the library, bound by its mangled
+    name for the tests that hold the capped kernels directly."""
+    global _randperm_capped
+    if _randperm_capped is None:
+        f = getattr(lib(), '_ZN2fs15randperm_deviceEPKlS1_S1_llPiPjiPv')
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                      C.c_void_p]
+        _randperm_capped = f
+    return _randperm_capped
+
+
 def get_tuning():
     """The fs_tuning the calling thread's next launch would use, as a dict (include/fedsim.h:
     the thread's own override, else the process-wide value)."""

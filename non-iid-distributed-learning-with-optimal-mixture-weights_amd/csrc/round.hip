@@ -38,6 +38,12 @@
 #include "finalize.h"
 #include "mse_rows.h"
 #include "mt_replay.h"
+#include "randperm_geom.h"
+
+// RP_CAPPED = 0 (build macro, A/B): the plan's replays keep the uncapped geometry everywhere
+#ifndef RP_CAPPED
+#define RP_CAPPED 1
+#endif
 
 namespace fs {
 
@@ -132,6 +138,7 @@ struct fs_plan {
   int64_t max_n = 0;
   int64_t max_client_steps = 0;       // E * ceil(max_j n_j / B)
   int fuse_E = 0;                     // evaluation blocks a TRAIN launch can carry (0: none)
+  int rp_idle = 0;                    // CUs a TRAIN launch leaves idle for a device replay beside it (0: no cap)
   int eval_pending = -1;              // round whose evaluation rides on the next TRAIN launch
   int fin_pending = -1;               // round whose fused evaluation awaits its finaliser (it rides
                                       // on the next AGGREGATE launch, fs_plan_round)
@@ -270,6 +277,16 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
       p->fuse_E = (int)std::min<int64_t>(idle, (d.n_t + 15) / 16);
     }
   }
+  // A device replay that runs beside a parallel exchanging TRAIN launch stays on some of the CUs
+  // that launch leaves idle, the same number on every XCD (rp_cap_blocks, randperm_geom.h; DESIGN
+  // 4.4): a group needs every partner resident, and a replay wave on a CU a group needs holds the
+  // whole launch up for the length of a pass.  Launches that leave fewer than 16 CUs idle, chained
+  // launches and FedAMW's replay (shuffle_after_train: beside the Z GEMM) keep the uncapped geometry.
+  // (The cap's "at most half of an XCD's idle CUs" is there for the fused evaluation's blocks; it
+  // holds whether or not this plan fuses one -- fuse_E == 0 with no_eval_fuse or no test set -- since
+  // the replay ends inside its chunk on that share anyway: one rule, not two.)
+  if (RP_CAPPED && d.shuffle_device && d.loss == 0 && d.G > 1 && !d.chained && !d.shuffle_after_train)
+    p->rp_idle = fs::split_idle_cus(d.N, d.C, d.B, d.ld, d.G, 0);
   hipError_t e = hipSuccess;
   for (int s = 0; s < 2 && e == hipSuccess; ++s) {
     if (!d.shuffle_device) {
@@ -323,6 +340,11 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
   return FS_OK;
 }
 
+// the workgroups a replay of `npasses` passes, the shuffles of `rounds` rounds, may take (0: no cap)
+static int plan_rp_cap(const fs_plan* p, int64_t npasses, int rounds) {
+  return fs::rp_cap_blocks(p->rp_idle, npasses, p->max_n, rounds);
+}
+
 // Device replay: upload the seeds and launch fs_randperm_device on the side stream.
 static int device_shuffle(fs_plan* p, const int64_t* h_seeds, int t) {
   const int s = t & 1;
@@ -339,7 +361,8 @@ static int device_shuffle(fs_plan* p, const int64_t* h_seeds, int t) {
            "fs_plan_shuffle");
   const int64_t* seeds = p->seed_copy ? p->d_seed[k] : p->h_seed_dev[k];
   // (no error word: p->max_n is the maximum of the plan's own pass sizes)
-  const int rc = fs_randperm_device(seeds, p->d_pass, p->d_pass + P, P, p->max_n, p->d_perm[s], nullptr, p->copy);
+  const int rc = fs::randperm_device(seeds, p->d_pass, p->d_pass + P, P, p->max_n, p->d_perm[s], nullptr,
+                                     plan_rp_cap(p, P, 1), p->copy);
   if (rc != FS_OK) return rc;
   FS_HIP(hipEventRecord(p->seed_read[k], p->copy), "fs_plan_shuffle");
   p->seed_pending[k] = true;
@@ -410,8 +433,8 @@ static int launch_chunk(fs_plan* p) {
              "fs_plan_shuffle");
     const int64_t* seeds = p->seed_copy ? p->d_seed[k] : p->h_seed_dev[k];
     // (no error word: the plan's max_n is the maximum of its own pass sizes, so no pass exceeds it)
-    const int rc = fs_randperm_device(seeds, p->d_pass_chunk, p->d_pass_chunk + KP, nr * P, p->max_n, p->d_perm[s],
-                                      nullptr, p->copy);
+    const int rc = fs::randperm_device(seeds, p->d_pass_chunk, p->d_pass_chunk + KP, nr * P, p->max_n, p->d_perm[s],
+                                       nullptr, plan_rp_cap(p, nr * P, nr), p->copy);
     if (rc != FS_OK) return rc;
   }
   FS_HIP(hipEventRecord(p->seed_read[k], p->copy), "fs_plan_shuffle");

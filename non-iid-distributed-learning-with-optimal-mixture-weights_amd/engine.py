@@ -71,8 +71,12 @@ class Shuffler:
     trains (``prepare``), ordered by events: a slot is rewritten only after the kernel
     that consumed it has finished (``consumed``), and read only after it is ready."""
 
-    def __init__(self, ns, offs, size, device, max_n=None):
+    def __init__(self, ns, offs, size, device, max_n=None, max_blocks=0):
         self.P = int(len(ns))
+        # internal: > 0 replays through fs::randperm_device in the capped, persistent geometry of at
+        # most this many workgroups (what the round plan asks for beside a training launch); 0 is
+        # fs_randperm_device, the C ABI's geometry
+        self.max_blocks = int(max_blocks)
         # the launch contract (include/fedsim.h): max_n bounds every pass; a caller may pass a
         # smaller value only to exercise the error path (check_errors then raises)
         self.max_n = int(max_n) if max_n is not None else (int(np.max(ns)) if self.P else 0)
@@ -101,7 +105,13 @@ class Shuffler:
             ev = torch.cuda.Event()
             ev.record(stream)
             self.host_free[slot] = ev
-            if self.P:
+            if self.P and self.max_blocks > 0:
+                _lib.check(_lib.randperm_device_capped()(_lib.ptr(self.seed_dev[slot]), _lib.ptr(self.n_dev),
+                                                         _lib.ptr(self.off_dev), self.P, self.max_n,
+                                                         _lib.ptr(self.bufs[slot]), _lib.ptr(self.err),
+                                                         self.max_blocks, _lib.stream_ptr(stream)),
+                           'fs::randperm_device')
+            elif self.P:
                 _lib.check(_lib.lib().fs_randperm_device(_lib.ptr(self.seed_dev[slot]), _lib.ptr(self.n_dev),
                                                          _lib.ptr(self.off_dev), self.P, self.max_n,
                                                          _lib.ptr(self.bufs[slot]), _lib.ptr(self.err),
