@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 20
+#define FS_ABI_VERSION 21
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -213,7 +213,8 @@ int fs_randperm_device(const int64_t* d_seeds, const int64_t* d_n, const int64_t
  *   d_W_start  [C][ld]         round-start weights (client 0's start when chained)
  *   d_W_out    [N][C][ld]      each client's trained weights (the clients x params buffer)
  *   d_loss     [N] double      last-epoch |b|-weighted mean loss (incl. prox/ridge terms)
- *   B, E       batch size (<= 64), local epochs
+ *   B, E       batch size (>= 1; above 64: the wide form, G = 1 | FS_G_WIDE), local epochs.  The
+ *              effective batch of client j is min(B, n_j).
  *   lr, mu, lam, prox, reg     SGD lr; prox weight (used iff prox); ridge weight (iff reg)
  *   chained    1: client j starts from client j-1's result and its prox anchor is
  *              that start (reference semantics);  0: every client starts
@@ -247,11 +248,24 @@ int fs_randperm_device(const int64_t* d_seeds, const int64_t* d_n, const int64_t
  *              one workgroup per client, 2..16 = that split width if the shape allows it,
  *              G | FS_G_PAIR = the pair form, G | FS_G_TEAMS = the team form at that width
  *              if the shape allows it); prox says whether the FedProx term is on.
- * Requires 1 <= C <= 32, B <= 64, ld % 64 == 0, D <= ld.
+ *              1 | FS_G_WIDE (ABI 21, any B >= 1, C <= 32, parallel or chained clients): the
+ *              "wide" form -- one workgroup per client with the batch walked in 64-row blocks:
+ *              every block's forward on the step's unchanged weights, g = (softmax - onehot) /
+ *              |b| over the whole batch, the gradient accumulated over all blocks and one
+ *              fused update per batch.  min(N, 512) workgroups walk d_order (chained: one), each
+ *              with a slot of d_ws for its batch's g: [ceil64(min(B, max_j n_j))][16 or 32]
+ *              floats; the last 256 bytes stay the error block, which this form never writes.
+ *              fs_local_train_plan answers 1 | FS_G_WIDE for B > 64, and for a request of
+ *              1 | FS_G_WIDE at any B; its ws_bytes comes from max_en / E (the largest client)
+ *              and the workgroups launched -- host arithmetic only, the same on every device.
+ *              A client whose batch outgrows the slot (a workspace planned for other clients)
+ *              is not trained: its start comes back with a NaN loss.
+ * Requires 1 <= C <= 32, B >= 1 (B <= 64 without FS_G_WIDE), ld % 64 == 0, D <= ld.
  * ------------------------------------------------------------------------- */
 #define FS_G_PAIR 256
 #define FS_G_TEAMS 512
 #define FS_G_PIPE 1024
+#define FS_G_WIDE 2048
 int fs_local_train_plan(int N, int C, int B, int E, int64_t ld, int64_t max_en, int chained, int prox,
                         int* G_out, int64_t* ws_bytes_out);
 int fs_local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
@@ -485,7 +499,8 @@ int fs_mix_solve_plan(int N, int C, int n_val, int epochs, int Bv, int blocks, f
  * launched -- FS_LT_SINGLE (1, one workgroup per client), FS_LT_SPLIT (2), FS_LT_DBUF (3, the
  * split form's double-buffered instance: the rows streamed ahead of the hand-off),
  * FS_LT_PAIR (4), FS_LT_PIPE (5), FS_LT_TEAMS (6), FS_LT_MB (7, ABI 16: the split form's
- * 4x4x1 multi-block instances, fs_tuning.split_mb); 0 = none yet. */
+ * 4x4x1 multi-block instances, fs_tuning.split_mb), FS_LT_WIDE (8, ABI 21: the batch-tiled
+ * form, G = 1 | FS_G_WIDE); 0 = none yet. */
 #define FS_LT_SINGLE 1
 #define FS_LT_SPLIT 2
 #define FS_LT_DBUF 3
@@ -493,6 +508,7 @@ int fs_mix_solve_plan(int N, int C, int n_val, int epochs, int Bv, int blocks, f
 #define FS_LT_PIPE 5
 #define FS_LT_TEAMS 6
 #define FS_LT_MB 7
+#define FS_LT_WIDE 8
 int fs_local_train_last_kernel(void);
 
 /* ------------------------------------------------------------------------- *

@@ -93,13 +93,15 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
 G_TEAMS = 512            # fs_local_train_plan: G | G_TEAMS = the team form at width G (ABI 13)
-LT_KERNELS = {1: 'single', 2: 'split', 3: 'dbuf', 4: 'pair', 5: 'pipe', 6: 'teams', 7: 'mb'}   # fs_local_train_last_kernel (ABI 15; mb: 16)
+LT_KERNELS = {1: 'single', 2: 'split', 3: 'dbuf', 4: 'pair', 5: 'pipe', 6: 'teams', 7: 'mb',
+              8: 'wide'}   # fs_local_train_last_kernel (ABI 15; mb: 16; wide: 21)
 G_PIPE = 1024            # fs_local_train_plan: G | G_PIPE = the pipelined split form at width G (ABI 14)
+G_WIDE = 2048            # fs_local_train_plan: 1 | G_WIDE = the batch-tiled form, any batch size (ABI 21)
 ERR_BLOCK = 256          # the error block at the end of every exchange workspace (include/fedsim.h)
 SOLVER_NAMES = {0: 'none', 1: 'reg', 2: 'mc', 3: 'staged', 4: 'global', 5: 'reg2', 6: 'wave', 8: 'quad', 9: 'qmc', 10: 'bin'}
 SOLVERS = {v: k for k, v in SOLVER_NAMES.items() if k}
@@ -314,6 +316,7 @@ KERNEL_SOURCES = {
                     'eval_rows.h', 'lanes.h'),
     'mix_solve': ('mixture.hip', 'mixture_forms.h', 'common.h', 'lanes.h'),
     'mix_z': ('mix_z.hip', 'common.h'),
+    'local_train_wide': ('local_train_wide.hip', 'local_train_wide.h', 'common.h'),
     'local_train_mse': ('local_train_mse.hip', 'mse_rows.h', 'common.h'),
     'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),
     'z_eval': ('z_eval.hip', 'common.h'),

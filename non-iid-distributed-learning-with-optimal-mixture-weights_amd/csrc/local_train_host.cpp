@@ -1,17 +1,20 @@
 // Host side of fs_local_train: the geometry of every exchanging form (split with its team
 // instances, pair, pipe), the planner (fs_local_train_plan), the exchange workspace's layout and
-// hand-off tags, the launch setup the forms share, and fs_local_train's validation and dispatch.
+// hand-off tags, the launch setup the forms share, the wide form's workspace (local_train_wide.h:
+// one workgroup per client, nothing exchanged), and fs_local_train's validation and dispatch.
 // Host code only (built without a device pass): the kernels and their instance selection stay in
 // local_train*.hip, behind one launch_<form>_instance each (local_train_forms.h), so an edit
 // here changes no kernel revision (_lib.source_revision).
 #include <mutex>
 #include <unordered_map>
 
+#include "local_train_wide.h"
 #include "split_common.h"
 
 namespace fs {
 
-static_assert(SP_ERR_BYTES == PR_ERR_BYTES && SP_ERR_BYTES == PP_ERR_BYTES, "one error block for every form");
+static_assert(SP_ERR_BYTES == PR_ERR_BYTES && SP_ERR_BYTES == PP_ERR_BYTES && SP_ERR_BYTES == WD_ERR_BYTES,
+              "one error block for every form");
 
 // CUs of the current device (cached)
 static int device_cus() {
@@ -171,6 +174,7 @@ static int64_t form_ws_bytes(const Form& f, int N, int G, int B, int chained, in
 }
 
 int split_idle_cus(int N, int C, int B, int64_t ld, int G, int chained) {
+  if (G & FS_G_WIDE) return 0;           // one workgroup per client: not an exchanging launch
   const Form& f = form_of(G);
   const int g = G & (FS_G_PAIR - 1);
   const int cus = device_cus();
@@ -241,6 +245,31 @@ static int exchange_setup(const Form& f, const LTParams& P, int G, void* ws, int
   return FS_OK;
 }
 
+// ---- the wide form (local_train_wide.hip): one workgroup per client, any batch size ---------------
+// Host arithmetic only (no device query): wd_grid(N, chained) workgroups, each with a slot of
+// [wd_slot_rows(largest batch)][wd_nc(C)] floats, then the error block (never written).
+
+// bmax: the largest effective batch, min(B, max_j n_j)
+static int64_t wide_ws_bytes(int N, int C, int64_t bmax, int chained) {
+  return (int64_t)wd_grid(N, chained) * wd_slot_rows(bmax) * wd_nc(C) * (int64_t)sizeof(float) + WD_ERR_BYTES;
+}
+
+// lays `grid` slots out over the workspace the caller planned: the slot is as many whole
+// blocks of rows as the bytes before the error block give every workgroup
+static int wide_setup(const LTParams& P, void* ws, int64_t ws_bytes, WideWS& X, int& grid) {
+  grid = wd_grid(P.N, P.chained);
+  if (!ws || ws_bytes < WD_ERR_BYTES) return fail(FS_EINVAL, "fs_local_train: workspace too small");
+  const int64_t row_bytes = (int64_t)wd_nc(P.C) * (int64_t)sizeof(float);
+  int64_t rows = (ws_bytes - WD_ERR_BYTES) / grid / row_bytes / WD_BLOCK * WD_BLOCK;
+  // (no more than B asks for, and an int: client sizes are ints, so no batch is longer)
+  rows = std::min<int64_t>({rows, wd_slot_rows((int64_t)P.B), (int64_t)INT32_MAX / WD_BLOCK * WD_BLOCK});
+  if (P.E > 0 && rows < WD_BLOCK) return fail(FS_EINVAL, "fs_local_train: workspace too small");
+  X.g = reinterpret_cast<float*>(ws);
+  X.slot_rows = (int)rows;
+  X.slot_floats = (int64_t)X.slot_rows * wd_nc(P.C);
+  return FS_OK;
+}
+
 static thread_local int t_last_lt = 0;
 void set_last_lt_kernel(int k) { t_last_lt = k; }
 
@@ -251,13 +280,16 @@ int local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const 
                 int64_t max_client_steps, const FuseEval* fuse) {
   FS_REQUIRE(N >= 1, "N must be >= 1");
   FS_REQUIRE(C >= 1 && C <= 32, "num_classes must be in [1, 32]");
-  FS_REQUIRE(B >= 1 && B <= 64, "batch_size must be in [1, 64]");
+  const bool wide = (G & FS_G_WIDE) != 0;
+  FS_REQUIRE(B >= 1, "batch_size must be >= 1");
+  FS_REQUIRE(wide || B <= 64, "batch_size above 64 needs the wide form (G = 1 | FS_G_WIDE, from fs_local_train_plan)");
+  FS_REQUIRE(!wide || G == (1 | FS_G_WIDE), "the wide form runs one workgroup per client (G = 1 | FS_G_WIDE)");
   FS_REQUIRE(E >= 0, "epoch must be >= 0");
   FS_REQUIRE(ld >= 64 && ld % 64 == 0, "ld must be a positive multiple of 64");
   FS_REQUIRE(d_phi && d_row_off && d_labels && d_perms && d_W_start && d_W_out && d_loss, "null pointer");
   LTParams P{d_phi, ld, d_row_off, d_labels, d_perms, d_order, N, C, B, E, lr, mu, lam,
              prox ? 1 : 0, reg ? 1 : 0, chained ? 1 : 0, d_W_start, d_W_out, d_loss, max_client_steps};
-  if (fuse && G > 1 && !chained) {
+  if (fuse && G > 1 && !wide && !chained) {
     P.fuse_phi = fuse->phi;
     P.fuse_y = fuse->y;
     P.fuse_n = fuse->n;
@@ -265,7 +297,13 @@ int local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const 
     P.fuse_part = fuse->part;
   }
   int rc;
-  if (G > 1) {
+  if (wide) {
+    set_last_lt_kernel(FS_LT_WIDE);
+    WideWS X;
+    int grid = 0;
+    rc = wide_setup(P, d_ws, ws_bytes, X, grid);
+    if (rc == FS_OK) rc = launch_local_train_wide(P, X, grid, st);
+  } else if (G > 1) {
     const Form& f = form_of(G);
     const int g = G & (FS_G_PAIR - 1);
     set_last_lt_kernel(f.kernel);
@@ -303,17 +341,26 @@ extern "C" int fs_local_train(const float* d_phi, int64_t ld, const int64_t* d_r
 // workspace bytes it needs.  On entry *G_out is a request: 0 = let the planner choose,
 // 1 = one workgroup per client, 2..16 = that group width if the shape allows it (else the
 // planner's choice), width | FS_G_* = that form at that width, likewise.
+// B > 64, or a request of 1 | FS_G_WIDE at any B: the wide form (1 | FS_G_WIDE), whose workspace
+// is wd_grid(N, chained) slots for the largest effective batch, min(B, max_en / E) rows -- host
+// arithmetic only, the same answer on every device.
 // prox: the FedProx term is on (kept in the ABI; every split variant covers it).
 // max_en = max_j E * n_j.
 extern "C" int fs_local_train_plan(int N, int C, int B, int E, int64_t ld, int64_t max_en, int chained, int prox,
                                    int* G_out, int64_t* ws_bytes_out) {
   FS_REQUIRE(G_out && ws_bytes_out, "null pointer");
   FS_REQUIRE(N >= 1 && B >= 1 && ld >= 64 && ld % 64 == 0, "bad sizes");
-  (void)max_en;
-  (void)E;
   const int want = *G_out;
   *G_out = 1;
   *ws_bytes_out = 0;
+  if (B > 64 || want == (1 | FS_G_WIDE)) {
+    FS_REQUIRE(C >= 1 && C <= 32, "num_classes must be in [1, 32]");
+    FS_REQUIRE(E >= 0 && (E == 0 || max_en >= 1), "the wide form needs max_en = max_j E * n_j");
+    const int64_t max_n = E > 0 ? (max_en + E - 1) / E : 0;
+    *G_out = 1 | FS_G_WIDE;
+    *ws_bytes_out = wide_ws_bytes(N, C, std::min<int64_t>(B, max_n), chained);
+    return FS_OK;
+  }
   const int cus = device_cus();
   if (want == 1 || C > 16 || B > 32 || cus <= 0) return FS_OK;
   const int NT = (int)(ld >> 6);

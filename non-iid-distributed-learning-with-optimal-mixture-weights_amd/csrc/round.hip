@@ -271,7 +271,8 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
   // FS_PHASE_EVAL_DEFER: a parallel split launch that leaves CUs idle evaluates the previous
   // round's global model on them (fs_tuning.no_eval_fuse turns this off)
   // (the MSE plan never fuses: G == 1, fuse_E stays 0 and a deferred evaluation runs as a launch of its own)
-  if (d.loss == 0 && d.d_phi_t && d.n_t > 0 && d.d_labels_t && d.d_eval_ws && d.C <= 16 && d.G > 1 && !d.chained) {
+  if (d.loss == 0 && d.d_phi_t && d.n_t > 0 && d.d_labels_t && d.d_eval_ws && d.C <= 16 && d.G > 1 && !(d.G & FS_G_WIDE) &&
+      !d.chained) {   // (the wide form is one workgroup per client: nothing to fuse into, as under loss = 1)
     if (!fs::tuning().no_eval_fuse) {
       const int idle = fs::split_idle_cus(d.N, d.C, d.B, d.ld, d.G, 0);
       p->fuse_E = (int)std::min<int64_t>(idle, (d.n_t + 15) / 16);
@@ -285,7 +286,8 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
   // (The cap's "at most half of an XCD's idle CUs" is there for the fused evaluation's blocks; it
   // holds whether or not this plan fuses one -- fuse_E == 0 with no_eval_fuse or no test set -- since
   // the replay ends inside its chunk on that share anyway: one rule, not two.)
-  if (RP_CAPPED && d.shuffle_device && d.loss == 0 && d.G > 1 && !d.chained && !d.shuffle_after_train)
+  if (RP_CAPPED && d.shuffle_device && d.loss == 0 && d.G > 1 && !(d.G & FS_G_WIDE) && !d.chained &&
+      !d.shuffle_after_train)
     p->rp_idle = fs::split_idle_cus(d.N, d.C, d.B, d.ld, d.G, 0);
   hipError_t e = hipSuccess;
   for (int s = 0; s < 2 && e == hipSuccess; ++s) {

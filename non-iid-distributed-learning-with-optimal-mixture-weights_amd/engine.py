@@ -166,7 +166,9 @@ class LocalTrainer:
     mode as persistent groups over the clients -- two clients per group in the pair form
     (G | _lib.G_PAIR) where the shape allows it -- in chained mode as one group walking the
     chain); 1 forces one workgroup per client, G a split width, G | _lib.G_PAIR the pair form,
-    G | _lib.G_TEAMS the team form, G | _lib.G_PIPE the pipelined split form.
+    G | _lib.G_TEAMS the team form, G | _lib.G_PIPE the pipelined split form,
+    1 | _lib.G_WIDE the batch-tiled form (one workgroup per client, any batch size: what the
+    planner answers for B > 64).
 
     ``loss='mse'`` (the regression task: C = 1, float targets in ``feats``): fs_local_train_mse,
     one workgroup per client, no planner call and no workspace."""
@@ -201,6 +203,7 @@ class LocalTrainer:
             if split not in (None, 1):
                 raise _lib.FedsimError('fs_local_train_mse has no split form (one workgroup per client)')
             self.G, self.pair, self.teams, self.pipe, self.width, self.ws = 1, False, False, False, 1, None
+            self.wide = False
             return
         import ctypes
         g, wsb = ctypes.c_int(0 if split is None else int(split)), ctypes.c_int64(0)
@@ -215,14 +218,17 @@ class LocalTrainer:
         self.pair = bool(self.G & _lib.G_PAIR)
         self.teams = bool(self.G & _lib.G_TEAMS)
         self.pipe = bool(self.G & _lib.G_PIPE)
+        self.wide = bool(self.G & _lib.G_WIDE)      # one workgroup per client, the batch in 64-row blocks
         self.width = self.G & (_lib.G_PAIR - 1)     # workgroups per client group
         self.ws = (torch.zeros(max(2 * _lib.ERR_BLOCK, int(wsb.value)), dtype=torch.uint8, device=dev)
-                   if self.G > 1 else None)
+                   if (self.G > 1 or wsb.value > 0) else None)
 
     def groups(self, cus):
         """Client groups a launch of this trainer runs on ``cus`` CUs (fs_local_train_plan's rule)."""
         if self.G <= 1:
             return 1 if self.chained else self.N
+        if self.wide:                      # a persistent grid of at most 512 workgroups walks the clients
+            return 1 if self.chained else min(self.N, 512)
         if self.chained:
             return 1
         per = (self.N + 1) // 2 if (self.pair or self.teams) else self.N

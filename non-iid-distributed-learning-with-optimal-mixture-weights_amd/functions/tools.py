@@ -145,8 +145,11 @@ def _check_inputs(type, X_train, y_train, num_classes, batch_size, epoch, round,
             raise ValueError('num_samples should be a positive integer value, but got num_samples=0')
     if not (1 <= num_classes <= 32):
         raise NotImplementedError('num_classes must be in [1, 32]')
-    if not (1 <= batch_size <= 64):
-        raise NotImplementedError('batch_size must be in [1, 64]')
+    if batch_size < 1:
+        raise NotImplementedError('batch_size must be >= 1')
+    if type == 'regression' and batch_size > 64:
+        raise NotImplementedError("batch_size must be in [1, 64] for type='regression' (the MSE kernels have no "
+                                  "batch-tiled form; classification takes any batch_size)")
     if epoch < 1 or round < 0:
         raise ValueError('epoch must be >= 1 and round >= 0')
     if type == 'regression':
