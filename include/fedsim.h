@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 21
+#define FS_ABI_VERSION 22
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -304,6 +304,20 @@ int fs_local_train_mse(const float* d_phi, int64_t ld, const int64_t* d_row_off,
  * ------------------------------------------------------------------------- */
 int fs_aggregate(const float* d_W_all, int64_t stride, const float* d_p, int N, int64_t len,
                  float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 22) The gathered fold of a round with partial client participation:
+ * d_W_bar = q_0*W[sel_0] + q_1*W[sel_1] + ... + q_{M-1}*W[sel_{M-1}] in k order, every product
+ * and sum rounded separately (tools.py:345-350 over the sampled clients, ascending client id).
+ * W[j] = d_W_all + j*stride, len floats; d_sel [M] int32 row indices (each a valid row of
+ * d_W_all: the caller's contract, nothing on the device checks it), d_q [M] weights.
+ * Contract: bitwise what fs_aggregate returns on the compacted copy W[sel] with the same
+ * `chunks`, d_ws and ws_floats -- the same regimes chosen by M instead of N, so for M < 16 (or
+ * chunks == 1) the reference's exact left fold.  Rows outside d_sel are never read: the traffic
+ * is M*len floats plus the output, not N*len.  No atomics, no cross-workgroup wait.
+ * ------------------------------------------------------------------------- */
+int fs_aggregate_sel(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
+                     int64_t len, float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Test evaluation.  Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
@@ -655,6 +669,37 @@ int fs_plan_shuffle_flush(fs_plan* plan);
  * (0: the plan evaluates with launches of its own; fs_tuning.no_eval_fuse = 1 at creation
  * forces 0). */
 int fs_plan_eval_blocks(const fs_plan* plan);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 22) Partial client participation: a round in which only M <= N sampled clients train
+ * and are aggregated (McMahan's C; parallel clients, each from the round's d_W_g).
+ *   fs_plan_shuffle_subset  replays only the M*E passes of the sampled clients h_sel (host,
+ *                       strictly ascending ids in [0, N)) into slot t % 2, at the plan's usual
+ *                       offsets E*row_off[j] + e*n_j; h_seeds [M*E] sel-major / epoch-minor.
+ *                       Device replay: seeds and a per-round pass table in the pinned seed slot,
+ *                       one fs_randperm_device launch; host replay: the pool over the M*E passes.
+ *   fs_plan_round_subset    fs_plan_round over the sample: TRAIN launches the plan's training
+ *                       form over the M clients of d_sel_order (the ids of d_sel in dispatch
+ *                       order, longest first) on the unchanged d_W_out and
+ *                       d_loss_hist[t*N ..]: rows and entries of clients outside the sample are
+ *                       not written.  AGGREGATE is fs_aggregate_sel(d_W_out, d_sel, d_q, M) into
+ *                       d_W_g (d_sel ascending: the fold order).  EVAL / EVAL_DEFER as
+ *                       fs_plan_round: a deferred evaluation fuses into the subset TRAIN launch
+ *                       with the plan's block count (M <= N leaves no fewer CUs idle) and its
+ *                       finaliser rides on the gathered aggregate.
+ * d_sel, d_sel_order and d_q are device arrays read asynchronously: keep them alive (and
+ * unchanged) until the round's launches have run.  Rounds of both kinds may alternate on one
+ * plan; TRAIN returns FS_EINVAL when the slot was prepared for another client count.  Only the
+ * count is checked (the ids of the round call live on the device): passing the ids the shuffle
+ * call was given is the caller's contract -- a client of another sample would train on whatever
+ * shuffles its passes last received (zeros before the first: row 0 of the client every step).
+ * Returns FS_EUNSUPPORTED for a chained plan (the chain walkers index clients by position),
+ * FS_EINVAL for M < 1, M > N, a null pointer, ids not strictly ascending in range, or after
+ * fs_plan_set_shuffle_chunk(K > 1) (subset rounds use per-round slots).
+ * ------------------------------------------------------------------------- */
+int fs_plan_shuffle_subset(fs_plan* plan, const int64_t* h_seeds, const int32_t* h_sel, int M, int t);
+int fs_plan_round_subset(fs_plan* plan, int t, float lr, int phases, const int32_t* d_sel,
+                         const int32_t* d_sel_order, const float* d_q, int M, void* stream);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

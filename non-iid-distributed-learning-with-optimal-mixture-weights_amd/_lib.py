@@ -38,6 +38,8 @@ _SIGS = {
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fs_aggregate': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'fs_aggregate_sel': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -82,6 +84,9 @@ _SIGS = {
     'fs_plan_shuffle': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     'fs_plan_round': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     'fs_plan_eval_flush': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'fs_plan_shuffle_subset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    'fs_plan_round_subset': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p]),
     'fs_local_train_last_kernel': (C.c_int, []),
     'fs_plan_set_shuffle_chunk': (C.c_int, [C.c_void_p, C.c_int]),
     'fs_plan_shuffle_flush': (C.c_int, [C.c_void_p]),
@@ -93,7 +98,7 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)

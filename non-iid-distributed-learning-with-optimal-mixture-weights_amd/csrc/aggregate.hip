@@ -10,6 +10,7 @@
 // row is one coalesced sweep.  When C*ld/4 threads cannot fill the chip the client
 // range is cut into `chunks` consecutive pieces folded in parallel (stage 1) and the
 // partials are folded by a fixed tree (stage 2: strided in-order sums, then those in order).
+#include "aggregate_sel.h"
 #include "common.h"
 #include "finalize.h"
 
@@ -89,8 +90,8 @@ __global__ __launch_bounds__(256) void fold_partials_kernel(const float* __restr
 // instead of two, no workspace.  The round plan also hands it the deferred evaluation's
 // finaliser (one extra workgroup, eval.hip's eval_finalize arithmetic): config 2's round went
 // from four launches after the training (finalise, aggregate, fold, next training) to two.
-constexpr int AG_ONE_MAX_N = 512;   // above: 64 sub-ranges of 4 positions read 64-byte pieces of
-                                    // each client row (N = 1000-1250: 34-38 vs 18-19 us, round 5)
+// (AG_ONE_MAX_N = 512, aggregate_sel.h; above: 64 sub-ranges of 4 positions read 64-byte pieces of
+// each client row -- N = 1000-1250: 34-38 vs 18-19 us, round 5)
 
 template <int SUB>
 __global__ __launch_bounds__(256) void aggregate_one_kernel(const float* __restrict__ W, int64_t stride,
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void aggregate_one_kernel(const float* __restr
 // sub-ranges per position: 1 below 16 clients (then the fold is the reference's, bitwise),
 // else the largest power of two <= min(32, N / 6) (~6+ clients per thread: one or two round
 // trips of 8 loads)
-static int one_launch_sub(int N) {
+int one_launch_sub(int N) {
   if (N < 16) return 1;
   int s = 1;
   while (s * 2 <= 32 && s * 2 <= N / 6) s *= 2;
@@ -163,6 +164,31 @@ static void launch_one(const float* W, int64_t stride, const float* p, int N, in
   const int64_t blocks = (len4 + POS - 1) / POS + (fin.part ? 1 : 0);
   hipLaunchKernelGGL((aggregate_one_kernel<SUB>), dim3((unsigned)blocks), dim3(256), 0, st, W, stride, p, N, len4, per,
                      out, fin);
+}
+
+// the chunk rule of the two-stage form: how many consecutive client ranges (and clients per
+// range) N clients are folded in (chunks <= 0: by the shape)
+int aggregate_chunks(int N, int chunks, bool has_ws, int64_t ws_floats, int64_t len, int* per_out) {
+  if (chunks <= 0) {
+    // 8 chunks (>= 8 clients each): at N = 1000-1250 every count from 8 to 16 measured within
+    // 5 % of the best and the earlier "~2048 workgroups" rule (74-103 chunks) 10-20 % slower
+    // (profiles/r05/agg_time.txt)
+    chunks = (int)std::max<int64_t>(1, std::min<int64_t>(8, N / 8));
+  }
+  if (chunks > N) chunks = N;
+  // as many chunks as the workspace holds partials for (without one: a single chunk); an
+  // automatic count above that used to fall back to ONE chunk -- 8 % of HBM at config 4
+  // (1250 clients, 80 KB each, 5,120 threads walking all of them: 161 us per round)
+  if (chunks > 1) chunks = has_ws ? (int)std::min<int64_t>(chunks, ws_floats / len) : 1;
+  if (chunks < 1) chunks = 1;
+  const int per = (N + chunks - 1) / chunks;
+  *per_out = per;
+  return (N + per - 1) / per;
+}
+
+void fold_partials_launch(const float* d_part, int K, int64_t len4, float* d_out, hipStream_t st) {
+  hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)((len4 + FP_POS - 1) / FP_POS)), dim3(256), 0, st, d_part, K,
+                     len4, d_out);
 }
 
 int aggregate_launch(const float* d_W_all, int64_t stride, const float* d_p, int N, int64_t len, float* d_W_bar,
@@ -190,28 +216,15 @@ int aggregate_launch(const float* d_W_all, int64_t stride, const float* d_p, int
     if (rc != FS_OK) return rc;
   }
   const int64_t bx = (len4 + 255) / 256;
-  if (chunks <= 0) {
-    // 8 chunks (>= 8 clients each): at N = 1000-1250 every count from 8 to 16 measured within
-    // 5 % of the best and the earlier "~2048 workgroups" rule (74-103 chunks) 10-20 % slower
-    // (profiles/r05/agg_time.txt)
-    chunks = (int)std::max<int64_t>(1, std::min<int64_t>(8, N / 8));
-  }
-  if (chunks > N) chunks = N;
-  // as many chunks as the workspace holds partials for (without one: a single chunk); an
-  // automatic count above that used to fall back to ONE chunk -- 8 % of HBM at config 4
-  // (1250 clients, 80 KB each, 5,120 threads walking all of them: 161 us per round)
-  if (chunks > 1) chunks = d_ws ? (int)std::min<int64_t>(chunks, ws_floats / len) : 1;
-  if (chunks < 1) chunks = 1;
-  const int per = (N + chunks - 1) / chunks;
-  chunks = (N + per - 1) / per;
+  int per = 0;
+  chunks = aggregate_chunks(N, chunks, d_ws != nullptr, ws_floats, len, &per);
   if (chunks == 1) {
     hipLaunchKernelGGL(aggregate_kernel, dim3((unsigned)bx, 1), dim3(256), 0, st, d_W_all, stride, d_p, N, len4, per,
                        d_W_bar, (int64_t)0);
   } else {
     hipLaunchKernelGGL(aggregate_kernel, dim3((unsigned)bx, chunks), dim3(256), 0, st, d_W_all, stride, d_p, N, len4,
                        per, d_ws, len);
-    hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)((len4 + FP_POS - 1) / FP_POS)), dim3(256), 0, st, d_ws,
-                       chunks, len4, d_W_bar);
+    fold_partials_launch(d_ws, chunks, len4, d_W_bar, st);
   }
   FS_LAUNCH_CHECK();
   return FS_OK;

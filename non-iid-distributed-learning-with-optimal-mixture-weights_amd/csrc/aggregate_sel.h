@@ -1,0 +1,23 @@
+// What fs_aggregate (aggregate.hip) and fs_aggregate_sel (aggregate_sel.hip) share: the regime
+// threshold, the sub-range and chunk rules and the stage-2 fold, so the gathered fold takes the
+// same path as the contiguous one at the same client count -- its contract is bitwise equality.
+#pragma once
+#include "finalize.h"
+
+namespace fs {
+
+constexpr int AG_ONE_MAX_N = 512;   // clients up to which chunks <= 0 is the one-launch form
+
+int one_launch_sub(int N);          // sub-ranges per float4 position of the one-launch form
+// chunks and clients per chunk of the two-stage form (chunks <= 0: by the shape; clamped to the
+// partials the workspace holds)
+int aggregate_chunks(int N, int chunks, bool has_ws, int64_t ws_floats, int64_t len, int* per_out);
+// stage 2: K partials of 4 * len4 floats at d_part folded by the fixed tree into d_out
+void fold_partials_launch(const float* d_part, int K, int64_t len4, float* d_out, hipStream_t st);
+
+// fs_aggregate_sel with an optional finaliser (nullptr: none), as aggregate_launch
+int aggregate_sel_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
+                         int64_t len, float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks,
+                         const EvalFinalize* fin, hipStream_t st);
+
+}  // namespace fs

@@ -19,6 +19,12 @@
 //                       a coordinator thread, then one async upload of the permutations.
 // Events order the slots: a slot is rewritten only after the local training that
 // consumed its previous contents, and a local training waits for its slot.
+//
+// Partial participation (ABI 22, fs_plan_shuffle_subset / fs_plan_round_subset): a round in
+// which M <= N sampled clients train.  Only their M*E passes are replayed (into the usual slot
+// at the usual offsets), the plan's training form is launched over the M clients through its
+// `order` table on the unchanged W_out / loss history, and the aggregate gathers the M sampled
+// rows (fs_aggregate_sel).  Rows of W_out and the history outside the sample are not touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +40,7 @@
 #include <chrono>
 #include <cstdio>
 
+#include "aggregate_sel.h"
 #include "common.h"
 #include "finalize.h"
 #include "mse_rows.h"
@@ -117,6 +124,14 @@ class Pool {
 
 }  // namespace fs
 
+// a host shuffle job: round t, its seeds, and (a subset round) the sampled clients the
+// seeds belong to, sel-major (empty: every client)
+struct ShuffleJob {
+  int t = 0;
+  std::vector<int64_t> seeds;
+  std::vector<int32_t> sel;
+};
+
 struct fs_plan {
   fs_plan_desc d;
   std::vector<int64_t> n, off;         // per pass (j*E + e): rows, offset into the shuffle buffer
@@ -148,6 +163,7 @@ struct fs_plan {
   bool up_pending[2] = {false, false};
   bool cons_recorded[2] = {false, false};
   int slot_round[2] = {-1, -1};       // round whose shuffles slot s holds (set by the coordinator)
+  int slot_M[2] = {0, 0};             // clients whose passes that round's replay wrote (0: all N)
   // chunked device replay (fs_plan_set_shuffle_chunk, K > 1): slot s holds the shuffles of
   // the K rounds of chunk c (rounds cK .. cK+K-1), generated by ONE launch; the local
   // training waits for the slot once per chunk and records its release once per chunk, so
@@ -165,7 +181,7 @@ struct fs_plan {
   std::thread coord;
   std::mutex m;
   std::condition_variable cv, done;
-  std::deque<std::pair<int, std::vector<int64_t>>> jobs;
+  std::deque<ShuffleJob> jobs;
   bool stop = false;
 };
 
@@ -183,18 +199,18 @@ static int hip_fail(const char* what, hipError_t e) {
 
 extern "C" int64_t fs_plan_desc_size(void) { return (int64_t)sizeof(fs_plan_desc); }
 
-static int run_shuffle_job(fs_plan* p, const int64_t* h_seeds, int t);
+static int run_shuffle_job(fs_plan* p, const ShuffleJob& job);
 
 static void coordinator(fs_plan* p) {
   for (;;) {
-    std::pair<int, std::vector<int64_t>> job;
+    ShuffleJob job;
     {
       std::unique_lock<std::mutex> lk(p->m);
       p->cv.wait(lk, [p] { return p->stop || !p->jobs.empty(); });
       if (p->jobs.empty()) return;
       job = std::move(p->jobs.front());
     }
-    const int rc = run_shuffle_job(p, job.second.data(), job.first);
+    const int rc = run_shuffle_job(p, job);
     std::lock_guard<std::mutex> lk(p->m);
     p->jobs.pop_front();
     if (rc != FS_OK && p->job_status == FS_OK) {
@@ -233,6 +249,14 @@ extern "C" int fs_plan_destroy(fs_plan* p) {
   delete p->pool;
   delete p;
   return FS_OK;
+}
+
+// int64 entries of one pinned seed slot (and of its device copy) for chunks of `rounds` rounds of P
+// passes: the chunk's seeds [rounds][P] -- and never fewer than 3 * P, since a subset round lays
+// its seeds and its pass table out as [3][P] (device_shuffle_subset) whenever the chunk is 1,
+// whatever the chunk was set to before
+static int64_t seed_slot_entries(int64_t P, int rounds) {
+  return std::max<int64_t>(1, std::max<int64_t>((int64_t)rounds * P, 3 * P));
 }
 
 extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
@@ -295,6 +319,10 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
       e = hipHostMalloc(reinterpret_cast<void**>(&p->h_perm[s]), sizeof(int32_t) * p->perm_len, hipHostMallocDefault);
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_perm[s]), sizeof(int32_t) * p->perm_len);
+    // zeroed once: a subset round's replay writes the sampled clients' passes only, and a pass
+    // never written must still index inside its client (row 0) should a caller train it
+    if (e == hipSuccess) e = hipMemset(p->d_perm[s], 0, sizeof(int32_t) * p->perm_len);
+    if (e == hipSuccess && p->h_perm[s]) std::memset(p->h_perm[s], 0, sizeof(int32_t) * p->perm_len);
     // ordering-only events: no timestamps and no system-scope release when they complete (the
     // waits are device-side, and the host only needs the seed upload's completion, not the
     // visibility of device writes)
@@ -307,7 +335,8 @@ extern "C" int fs_plan_create(const fs_plan_desc* desc, fs_plan** out) {
     // (round 2, r02s2: no slower than a hipMemcpyAsync upload, and no copy on the side stream)
     p->seed_copy = false;
     for (int k = 0; k < fs_plan::SEED_SLOTS && e == hipSuccess; ++k) {
-      e = hipHostMalloc(reinterpret_cast<void**>(&p->h_seed[k]), sizeof(int64_t) * std::max<int64_t>(1, P),
+      // [3][P]: the seeds, then a subset round's pass table (rows, offset of each sampled pass)
+      e = hipHostMalloc(reinterpret_cast<void**>(&p->h_seed[k]), sizeof(int64_t) * seed_slot_entries(P, 1),
                         p->seed_copy ? hipHostMallocDefault : (hipHostMallocMapped | hipHostMallocCoherent));
       if (e == hipSuccess && !p->seed_copy)
         e = hipHostGetDevicePointer(reinterpret_cast<void**>(&p->h_seed_dev[k]), p->h_seed[k], 0);
@@ -371,6 +400,42 @@ static int device_shuffle(fs_plan* p, const int64_t* h_seeds, int t) {
   FS_HIP(hipEventRecord(p->uploaded[s], p->copy), "fs_plan_shuffle");
   p->up_pending[s] = true;
   p->slot_round[s] = t;
+  p->slot_M[s] = 0;
+  return FS_OK;
+}
+
+// Device replay of a subset round: the M*E sampled passes only.  Their seeds and a per-round pass
+// table (rows and offset of each sampled pass, the plan's own offsets E*row_off[j] + e*n_j) go
+// side by side into the pinned seed slot, which one fs::randperm_device launch reads.
+static int device_shuffle_subset(fs_plan* p, const int64_t* h_seeds, const int32_t* h_sel, int M, int t) {
+  const int s = t & 1;
+  const int E = p->d.E;
+  const int64_t P = (int64_t)p->n.size(), PS = (int64_t)M * E;
+  const int k = t % fs_plan::SEED_SLOTS;
+  if (p->seed_pending[k]) FS_HIP(hipEventSynchronize(p->seed_read[k]), "fs_plan_shuffle_subset");   // pinned seeds free
+  int64_t* hs = p->h_seed[k];
+  std::memcpy(hs, h_seeds, sizeof(int64_t) * PS);
+  for (int i = 0; i < M; ++i)
+    for (int e = 0; e < E; ++e) {
+      const int64_t pass = (int64_t)h_sel[i] * E + e;
+      hs[P + (int64_t)i * E + e] = p->n[pass];
+      hs[2 * P + (int64_t)i * E + e] = p->off[pass];
+    }
+  if (p->cons_recorded[s]) FS_HIP(hipStreamWaitEvent(p->copy, p->consumed[s], 0), "fs_plan_shuffle_subset");
+  if (p->d.shuffle_after_train && p->cons_recorded[s ^ 1])
+    FS_HIP(hipStreamWaitEvent(p->copy, p->consumed[s ^ 1], 0), "fs_plan_shuffle_subset");
+  const int64_t* dev = p->h_seed_dev[k];
+  // (no error word: p->max_n bounds every pass of the plan; the cap is the plan's -- M <= N clients
+  // leave no fewer CUs idle than the N the cap was sized for)
+  const int rc = fs::randperm_device(dev, dev + P, dev + 2 * P, PS, p->max_n, p->d_perm[s], nullptr,
+                                     plan_rp_cap(p, PS, 1), p->copy);
+  if (rc != FS_OK) return rc;
+  FS_HIP(hipEventRecord(p->seed_read[k], p->copy), "fs_plan_shuffle_subset");
+  p->seed_pending[k] = true;
+  FS_HIP(hipEventRecord(p->uploaded[s], p->copy), "fs_plan_shuffle_subset");
+  p->up_pending[s] = true;
+  p->slot_round[s] = t;
+  p->slot_M[s] = M;
   return FS_OK;
 }
 
@@ -390,19 +455,22 @@ extern "C" int fs_plan_set_shuffle_chunk(fs_plan* p, int rounds) {
     p->d_perm[s] = nullptr;
     FS_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_perm[s]), sizeof(int32_t) * p->perm_len * rounds),
            "fs_plan_set_shuffle_chunk");
+    // zeroed as at creation (a pass no replay ever wrote indexes row 0 of its client)
+    FS_HIP(hipMemset(p->d_perm[s], 0, sizeof(int32_t) * p->perm_len * rounds), "fs_plan_set_shuffle_chunk");
   }
+  const int64_t slot = seed_slot_entries(P, rounds);
   for (int k = 0; k < fs_plan::SEED_SLOTS; ++k) {
     FS_HIP(hipHostFree(p->h_seed[k]), "fs_plan_set_shuffle_chunk");
     FS_HIP(hipFree(p->d_seed[k]), "fs_plan_set_shuffle_chunk");
     p->h_seed[k] = nullptr;
     p->d_seed[k] = nullptr;
-    FS_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_seed[k]), sizeof(int64_t) * KP,
+    FS_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_seed[k]), sizeof(int64_t) * slot,
                          p->seed_copy ? hipHostMallocDefault : (hipHostMallocMapped | hipHostMallocCoherent)),
            "fs_plan_set_shuffle_chunk");
     if (!p->seed_copy)
       FS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&p->h_seed_dev[k]), p->h_seed[k], 0),
              "fs_plan_set_shuffle_chunk");
-    FS_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_seed[k]), sizeof(int64_t) * KP), "fs_plan_set_shuffle_chunk");
+    FS_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_seed[k]), sizeof(int64_t) * slot), "fs_plan_set_shuffle_chunk");
   }
   if (p->d_pass_chunk) FS_HIP(hipFree(p->d_pass_chunk), "fs_plan_set_shuffle_chunk");
   p->d_pass_chunk = nullptr;
@@ -518,20 +586,63 @@ extern "C" int fs_plan_shuffle(fs_plan* p, const int64_t* h_seeds, int t) {
   {
     std::lock_guard<std::mutex> lk(p->m);
     if (p->job_status != FS_OK) return fail(p->job_status, p->job_error);
-    p->jobs.emplace_back(t, std::vector<int64_t>(h_seeds, h_seeds + p->n.size()));
+    p->jobs.push_back(ShuffleJob{t, std::vector<int64_t>(h_seeds, h_seeds + p->n.size()), {}});
   }
   p->cv.notify_all();
   return FS_OK;
 }
 
-static int run_shuffle_job(fs_plan* p, const int64_t* h_seeds, int t) {
+// what both subset entry points reject (after their null and range checks)
+static int subset_admits(const fs_plan* p, const char* who) {
+  if (p->d.chained)
+    return fail(FS_EUNSUPPORTED, std::string(who) + ": chained plans walk the clients by position, not through the "
+                                                    "order table; subset rounds need parallel clients");
+  if (p->chunk > 1)
+    return fail(FS_EINVAL, std::string(who) + ": subset rounds use per-round shuffle slots (fs_plan_set_shuffle_chunk(1))");
+  return FS_OK;
+}
+
+// ABI 22: prepare a subset round's shuffles -- the M*E passes of the sampled clients h_sel
+// (strictly ascending client ids), seeds sel-major / epoch-minor -- into slot t % 2.
+extern "C" int fs_plan_shuffle_subset(fs_plan* p, const int64_t* h_seeds, const int32_t* h_sel, int M, int t) {
+  FS_REQUIRE(p && h_sel && t >= 0, "bad arguments");
+  FS_REQUIRE(M >= 1 && M <= p->d.N, "M must be in [1, N]");
+  FS_REQUIRE(h_seeds || p->n.empty(), "null pointer");
+  if (int rc = subset_admits(p, "fs_plan_shuffle_subset")) return rc;
+  for (int i = 0; i < M; ++i)
+    FS_REQUIRE(h_sel[i] >= 0 && h_sel[i] < p->d.N && (i == 0 || h_sel[i] > h_sel[i - 1]),
+               "sampled client ids must be strictly ascending and in [0, N)");
+  if (p->d.shuffle_device) {
+    if (p->n.empty()) {
+      p->slot_round[t & 1] = t;
+      p->slot_M[t & 1] = M;
+      return FS_OK;
+    }
+    return device_shuffle_subset(p, h_seeds, h_sel, M, t);
+  }
+  {
+    std::lock_guard<std::mutex> lk(p->m);
+    if (p->job_status != FS_OK) return fail(p->job_status, p->job_error);
+    p->jobs.push_back(ShuffleJob{t, std::vector<int64_t>(h_seeds, h_seeds + (int64_t)M * p->d.E),
+                                 std::vector<int32_t>(h_sel, h_sel + M)});
+  }
+  p->cv.notify_all();
+  return FS_OK;
+}
+
+static int run_shuffle_job(fs_plan* p, const ShuffleJob& job) {
+  const int t = job.t;
+  const int64_t* h_seeds = job.seeds.data();
   const int s = t & 1;
   if (p->up_pending[s]) FS_HIP(hipEventSynchronize(p->uploaded[s]), "fs_plan_shuffle");   // pinned slot free
   int32_t* out = p->h_perm[s];
+  const int E = p->d.E;
+  // a subset round: seed i belongs to pass sel[i / E] * E + i % E of the plan's table
   const std::function<void(int64_t)> one = [&](int64_t i) {
-    replay_randperm((uint64_t)h_seeds[i], p->n[i], out + p->off[i]);
+    const int64_t pass = job.sel.empty() ? i : (int64_t)job.sel[i / E] * E + i % E;
+    replay_randperm((uint64_t)h_seeds[i], p->n[pass], out + p->off[pass]);
   };
-  p->pool->run((int64_t)p->n.size(), one);
+  p->pool->run(job.sel.empty() ? (int64_t)p->n.size() : (int64_t)job.sel.size() * E, one);
   // the device slot is rewritten only after the local training that read it has finished
   if (p->cons_recorded[s]) FS_HIP(hipStreamWaitEvent(p->copy, p->consumed[s], 0), "fs_plan_shuffle");
   FS_HIP(hipMemcpyAsync(p->d_perm[s], out, sizeof(int32_t) * p->perm_len, hipMemcpyHostToDevice, p->copy),
@@ -540,6 +651,7 @@ static int run_shuffle_job(fs_plan* p, const int64_t* h_seeds, int t) {
   p->up_pending[s] = true;
   std::lock_guard<std::mutex> lk(p->m);
   p->slot_round[s] = t;
+  p->slot_M[s] = (int)job.sel.size();
   return FS_OK;
 }
 
@@ -551,13 +663,27 @@ static int plan_eval(const fs_plan_desc& d, int te, hipStream_t st) {
 }
 
 // round t's local training on the shuffles at `perms`, by the plan's loss
-static int plan_train(fs_plan* p, const int32_t* perms, int t, float lr, const fs::FuseEval* fuse, hipStream_t st) {
+// a subset round's sampled clients (fs_plan_round_subset): M ids ascending (the aggregate's fold
+// order) and in dispatch order (the training launch's), and their weights; all on the device
+struct Subset {
+  const int32_t* sel;
+  const int32_t* order;
+  const float* q;
+  int M;
+};
+
+// (a subset round: the same launch over the M clients of sub->order -- every form finds its
+// client through the order table, so W_out[j] and loss[j] stay indexed by client id)
+static int plan_train(fs_plan* p, const int32_t* perms, int t, float lr, const fs::FuseEval* fuse, const Subset* sub,
+                      hipStream_t st) {
   const fs_plan_desc& d = p->d;
   double* loss = d.d_loss_hist + (int64_t)t * d.N;
+  const int n = sub ? sub->M : d.N;
+  const int32_t* order = sub ? sub->order : d.d_order;
   if (d.loss)
-    return fs::local_train_mse(d.d_phi, d.ld, d.d_row_off, d.d_y, perms, d.d_order, d.N, d.B, d.E, lr, d.mu, d.prox,
+    return fs::local_train_mse(d.d_phi, d.ld, d.d_row_off, d.d_y, perms, order, n, d.B, d.E, lr, d.mu, d.prox,
                                d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out, loss, st);
-  return fs::local_train(d.d_phi, d.ld, d.d_row_off, d.d_labels, perms, d.d_order, d.N, d.C, d.B, d.E, lr, d.mu, d.prox,
+  return fs::local_train(d.d_phi, d.ld, d.d_row_off, d.d_labels, perms, order, n, d.C, d.B, d.E, lr, d.mu, d.prox,
                          d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out, loss, d.G, d.d_ws, d.ws_bytes, st,
                          p->max_client_steps, fuse);
 }
@@ -586,10 +712,10 @@ extern "C" int fs_plan_eval_flush(fs_plan* p, void* stream) {
   return flush_eval(p, st);
 }
 
-extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_override, void* stream) {
-  FS_REQUIRE(p && t >= 0, "bad arguments");
+// one round's launches; sub: the sampled clients of a subset round (nullptr: all N)
+static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_override, const Subset* sub,
+                      hipStream_t st) {
   const fs_plan_desc& d = p->d;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int s = t & 1;
   // a deferred evaluation rides on this TRAIN launch (it reads W_g before the launch
   // rewrites nothing but W_out); anything else that follows it runs it on its own first
@@ -622,7 +748,7 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
       FS_HIP(hipStreamWaitEvent(st, p->uploaded[sc], 0), "fs_plan_round");
       p->slot_waited[sc] = c;
     }
-    const int rc = plan_train(p, p->d_perm[sc] + (int64_t)r * p->perm_len, t, lr, fused ? &fuse : nullptr, st);
+    const int rc = plan_train(p, p->d_perm[sc] + (int64_t)r * p->perm_len, t, lr, fused ? &fuse : nullptr, nullptr, st);
     if (rc != FS_OK) return rc;
     if (r == p->slot_nrounds[sc] - 1) {            // the chunk's last round releases the slot
       FS_HIP(hipEventRecord(p->consumed[sc], st), "fs_plan_round");
@@ -634,14 +760,16 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
       std::unique_lock<std::mutex> lk(p->m);
       p->done.wait(lk, [&] {
         if (p->job_status != FS_OK || p->slot_round[s] == t) return true;
-        for (auto& j : p->jobs) if (j.first == t) return false;
+        for (auto& j : p->jobs) if (j.t == t) return false;
         return true;                               // never queued
       });
       if (p->job_status != FS_OK) return fail(p->job_status, p->job_error);
       if (p->slot_round[s] != t) return fail(FS_EINVAL, "fs_plan_round: shuffles of this round were not prepared");
+      if (p->slot_M[s] != (sub ? sub->M : 0))
+        return fail(FS_EINVAL, "fs_plan_round: this round's shuffles were prepared for another client count");
     }
     FS_HIP(hipStreamWaitEvent(st, p->uploaded[s], 0), "fs_plan_round");
-    const int rc = plan_train(p, p->d_perm[s], t, lr, fused ? &fuse : nullptr, st);
+    const int rc = plan_train(p, p->d_perm[s], t, lr, fused ? &fuse : nullptr, sub, st);
     if (rc != FS_OK) return rc;
     FS_HIP(hipEventRecord(p->consumed[s], st), "fs_plan_round");
     p->cons_recorded[s] = true;
@@ -654,21 +782,23 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
     p->fin_pending = t_eval;
   }
   if (phases & FS_PHASE_AGGREGATE) {
-    const float* pw = d_p_override ? d_p_override : d.d_p;
-    FS_REQUIRE(pw, "no mixture weights");
+    const float* pw = sub ? sub->q : d_p_override ? d_p_override : d.d_p;
+    if (!pw) return fail(FS_EINVAL, "fs_plan_round: no mixture weights");
     const int64_t len = (int64_t)d.C * d.ld;
     const fs::EvalFinalize fin = fin_of(p->fin_pending);
     const bool with_fin = p->fin_pending >= 0;
     p->fin_pending = -1;
-    const int rc = fs::aggregate_launch(d.d_W_out, len, pw, d.N, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats,
-                                        d.agg_chunks, with_fin ? &fin : nullptr, st);
+    const int rc = sub ? fs::aggregate_sel_launch(d.d_W_out, len, sub->sel, pw, sub->M, len, d.d_W_g, d.d_agg_ws,
+                                                  d.agg_ws_floats, d.agg_chunks, with_fin ? &fin : nullptr, st)
+                       : fs::aggregate_launch(d.d_W_out, len, pw, d.N, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats,
+                                              d.agg_chunks, with_fin ? &fin : nullptr, st);
     if (rc != FS_OK) return rc;
   }
   // (a finaliser still pending here is launched by the next fs_plan_round call -- any call that
   // trains or does not aggregate runs it first; results are read after such a call)
   if (phases & FS_PHASE_EVAL) {
-    FS_REQUIRE(d.d_phi_t && (d.loss ? (const void*)d.d_y_t : (const void*)d.d_labels_t) && d.d_eval_hist && d.d_eval_ws,
-               "no test set");
+    if (!(d.d_phi_t && (d.loss ? (const void*)d.d_y_t : (const void*)d.d_labels_t) && d.d_eval_hist && d.d_eval_ws))
+      return fail(FS_EINVAL, "fs_plan_round: no test set");
     if ((phases & FS_PHASE_EVAL_DEFER) && (p->fuse_E > 0 || d.loss)) {
       p->eval_pending = t;                         // evaluated by the next TRAIN launch (MSE: never fused,
       return FS_OK;                                // a launch of its own in the call that would have carried it)
@@ -677,4 +807,20 @@ extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const floa
     if (rc != FS_OK) return rc;
   }
   return FS_OK;
+}
+
+extern "C" int fs_plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_override, void* stream) {
+  FS_REQUIRE(p && t >= 0, "bad arguments");
+  return plan_round(p, t, lr, phases, d_p_override, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ABI 22: round t over the M sampled clients.  d_sel (ascending: the fold order), d_sel_order (the
+// same ids in dispatch order) and d_q are read asynchronously by the launches enqueued here.
+extern "C" int fs_plan_round_subset(fs_plan* p, int t, float lr, int phases, const int32_t* d_sel,
+                                    const int32_t* d_sel_order, const float* d_q, int M, void* stream) {
+  FS_REQUIRE(p && t >= 0 && d_sel && d_sel_order && d_q, "bad arguments");
+  FS_REQUIRE(M >= 1 && M <= p->d.N, "M must be in [1, N]");
+  if (int rc = subset_admits(p, "fs_plan_round_subset")) return rc;
+  const Subset sub{d_sel, d_sel_order, d_q, M};
+  return plan_round(p, t, lr, phases, nullptr, &sub, reinterpret_cast<hipStream_t>(stream));
 }

@@ -253,25 +253,48 @@ class LocalTrainer:
         the permutations are replayed on the GPU into shuffle slot ``slot``."""
         self.shuffler.prepare(seeds, slot, stream)
 
-    def run(self, W_start, lr, prox, mu, reg, lam, chained, slot=0, loss_out=None):
+    def sel_order(self, sel):
+        """The sampled client ids ``sel`` in dispatch order (longest first, stable: the LPT rule
+        of ``order`` restricted to them) as an int32 numpy array; validates the ids."""
+        sel = np.asarray(sel)
+        if sel.ndim != 1 or sel.size < 1 or sel.size > self.N or sel.dtype.kind not in 'iu':
+            raise ValueError('sel must be a 1-D array of 1 to %d client ids' % self.N)
+        sel = sel.astype(np.int64)
+        if int(sel.min()) < 0 or int(sel.max()) >= self.N or len(np.unique(sel)) != sel.size:
+            raise ValueError('sel: client ids must be distinct and lie in [0, %d)' % self.N)
+        sel = np.sort(sel)
+        steps = self.E * ((self.f.ns[sel] + self.B - 1) // self.B)
+        return sel[np.argsort(-steps, kind='stable')].astype(np.int32)
+
+    def run(self, W_start, lr, prox, mu, reg, lam, chained, slot=0, loss_out=None, sel=None):
         """Launch local training of every client; ``loss_out`` (float64 [N], default the
-        trainer's own buffer) receives the last-epoch losses."""
+        trainer's own buffer) receives the last-epoch losses.
+
+        ``sel`` (client ids; parallel clients only): a subset launch -- the same form over the
+        sampled clients alone, through its ``order`` table.  ``W_out[j]`` and ``loss[j]`` stay
+        indexed by client id; rows and entries of clients outside ``sel`` are not written."""
         f = self.f
         L = _lib.lib()
         loss = self.loss if loss_out is None else loss_out
+        n_run, order = self.N, self.order
+        if sel is not None:
+            if chained:
+                raise ValueError('a subset launch needs parallel clients (chained=False)')
+            order = torch.from_numpy(self.sel_order(sel)).to(f.device)
+            n_run = int(order.numel())
         perms = self.shuffler.acquire(slot)
         if self.task == 'mse':
             _lib.check(L.fs_local_train_mse(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), _lib.ptr(f.y),
-                                            _lib.ptr(perms), None if chained else _lib.ptr(self.order),
-                                            self.N, self.B, self.E, float(lr), float(mu), int(bool(prox)),
+                                            _lib.ptr(perms), None if chained else _lib.ptr(order),
+                                            n_run, self.B, self.E, float(lr), float(mu), int(bool(prox)),
                                             float(lam), int(bool(reg)), int(bool(chained)), _lib.ptr(W_start),
                                             _lib.ptr(self.W_out), _lib.ptr(loss), _lib.stream_ptr()),
                        'fs_local_train_mse')
             self.shuffler.release(slot)
             return self.W_out, loss
         _lib.check(L.fs_local_train(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev), _lib.ptr(f.labels),
-                                    _lib.ptr(perms), None if chained else _lib.ptr(self.order),
-                                    self.N, self.C, self.B, self.E, float(lr), float(mu), int(bool(prox)),
+                                    _lib.ptr(perms), None if chained else _lib.ptr(order),
+                                    n_run, self.C, self.B, self.E, float(lr), float(mu), int(bool(prox)),
                                     float(lam), int(bool(reg)), int(bool(chained)), _lib.ptr(W_start),
                                     _lib.ptr(self.W_out), _lib.ptr(loss), self.G, _lib.ptr(self.ws),
                                     0 if self.ws is None else self.ws.numel(), _lib.stream_ptr()),
@@ -353,6 +376,28 @@ class RoundPlan:
         assert seeds.shape == (self.npasses,)
         _lib.check(_lib.lib().fs_plan_shuffle(self._h, seeds.ctypes.data, int(t)), 'fs_plan_shuffle')
 
+    def shuffle_subset(self, seeds, sel, t):
+        """fs_plan_shuffle_subset: replay only the passes of the sampled clients ``sel`` (ascending
+        ids) of round t; seeds [len(sel) * E], sel-major / epoch-minor."""
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int64)
+        assert seeds.shape == (sel.size * self._desc.E,)
+        _lib.check(_lib.lib().fs_plan_shuffle_subset(self._h, seeds.ctypes.data, sel.ctypes.data, int(sel.size),
+                                                     int(t)), 'fs_plan_shuffle_subset')
+
+    def round_subset(self, t, lr, phases, sel, sel_order, q, M=None):
+        """fs_plan_round_subset: round t over the sampled clients.  ``sel`` (ascending ids),
+        ``sel_order`` (the same ids in dispatch order) int32 and ``q`` float32 are DEVICE tensors
+        the launches read asynchronously: the caller keeps them alive and unchanged."""
+        M = int(sel.numel()) if M is None else int(M)
+        for x, dt in ((sel, torch.int32), (sel_order, torch.int32), (q, torch.float32)):
+            if not (x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= M):
+                raise ValueError('round_subset: sel / sel_order (int32) and q (float32) must be contiguous device '
+                                 'tensors of at least M entries')
+        _lib.check(_lib.lib().fs_plan_round_subset(self._h, int(t), float(lr), int(phases), _lib.ptr(sel),
+                                                   _lib.ptr(sel_order), _lib.ptr(q), M, _lib.stream_ptr()),
+                   'fs_plan_round_subset')
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -383,6 +428,28 @@ class Aggregator:
         _lib.check(_lib.lib().fs_aggregate(_lib.ptr(W_all), self.len, _lib.ptr(p), self.N, self.len, _lib.ptr(out),
                                            _lib.ptr(self.ws), self.ws.numel(), int(self.chunks), _lib.stream_ptr()),
                    'fs_aggregate')
+        return out
+
+    def run_sel(self, W_all, sel, q, out, check=True):
+        """fs_aggregate_sel: ``out = sum_k q[k] * W_all[sel[k]]`` in k order, bitwise ``run`` on the
+        compacted copy ``W_all[sel]`` (an Aggregator of len(sel) clients with the same ``chunks``
+        and workspace).  ``sel`` int32 and ``q`` float32: device tensors of equal length; rows of
+        ``W_all`` outside ``sel`` are never read.  ``check`` reads ``sel`` back to hold it to the rows
+        of ``W_all`` (it synchronises; ``check=False`` for a ``sel`` validated before, as in a timed
+        loop -- nothing on the device checks the ids)."""
+        M = int(sel.numel())
+        if not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and q.is_cuda
+                and q.dtype == torch.float32 and q.is_contiguous() and q.numel() == M and M >= 1):
+            raise ValueError('run_sel: sel (int32) and q (float32) must be contiguous device tensors of equal, '
+                             'non-zero length')
+        if check:
+            rows = W_all.numel() // self.len
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_sel: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_sel(_lib.ptr(W_all), self.len, _lib.ptr(sel), _lib.ptr(q), M, self.len,
+                                               _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
+                                               _lib.stream_ptr()), 'fs_aggregate_sel')
         return out
 
 

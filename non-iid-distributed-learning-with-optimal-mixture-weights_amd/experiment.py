@@ -87,7 +87,8 @@ def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None
 
 def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batch_size=32, n_repeats=1,
         alpha_Dirk=0.01, data_dir='../FedAMW/datasets/', result_dir='./results', save=True, clients='sequential',
-        algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None):
+        algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None, participation=None,
+        sample_seed=0):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
@@ -109,6 +110,15 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
     acc_mat = np.empty((6, Round, n_repeats))
     hete_mat = np.empty(n_repeats)
     timing = {}
+    # partial participation (FedAvg and FedProx only, which then run with parallel clients):
+    # participants[k][repeat] = the R sampled id arrays of algorithm k's call
+    participants = [None] * len(NAMES)
+
+    def keep_participants(name, st):
+        if participation is not None:
+            k = NAMES.index(name)
+            participants[k] = (participants[k] or []) + [st['participants']]
+
     for t in range(n_repeats):
         d = prepare(dataset, D, num_partitions, alpha_Dirk, P, data_dir, synth=synth, verbose=verbose)
         C = d['num_classes'] if task == 'classification' else C
@@ -116,6 +126,8 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
         a = (d['X_train'], d['y_train'], d['X_test'], d['y_test'])
         kw = dict(verbose=verbose)
         par = dict(clients=clients, **kw)
+        fpar = par if participation is None else dict(clients='parallel', participation=participation,
+                                                      sample_seed=sample_seed, **kw)
 
         def timed(name, fn):
             t0 = time.perf_counter()
@@ -155,12 +167,20 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
                                                                      stats=ce('FedAMW_OneShot', True), **kw))
             train_mat[2, :, t], error_mat[2, :, t], acc_mat[2, :, t] = float(r[0]), r[1].numpy(), r[2].numpy()
         if 'FedAvg' in algos:
+            st = ce('FedAvg', False)
+            if participation is not None:
+                st = st or {}                  # always a stats dict: it carries the participants
             r = timed('FedAvg', lambda: tools.FedAvg(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False, 0,
-                                                     Round, stats=ce('FedAvg', False), **par))
+                                                     Round, stats=st, **fpar))
+            keep_participants('FedAvg', st)
             train_mat[3, :, t], error_mat[3, :, t], acc_mat[3, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         if 'FedProx' in algos:
+            st = ce('FedProx', False)
+            if participation is not None:
+                st = st or {}                  # always a stats dict: it carries the participants
             r = timed('FedProx', lambda: tools.FedProx(*a, task, C, D, lr, local_epoch, batch_size, True, mu, False,
-                                                       0, Round, stats=ce('FedProx', False), **par))
+                                                       0, Round, stats=st, **fpar))
+            keep_participants('FedProx', st)
             train_mat[4, :, t], error_mat[4, :, t], acc_mat[4, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         if 'FedAMW' in algos:
             r = timed('FedAMW', lambda: tools.FedAMW(*a, d['validloader'], task, C, D, lr, local_epoch, batch_size,
@@ -176,6 +196,8 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
     data_ = {'epochs': Round, 'train_loss': train_mat, 'test_loss': error_mat, 'test_acc': acc_mat,
              'heterogeneity': hete_mat, 'name': list(NAMES), 'seconds': {k: list(v) for k, v in timing.items()}}
     data_.update(cev)
+    if participation is not None:
+        data_['participants'] = participants
     if save:
         os.makedirs(result_dir, exist_ok=True)
         with open(os.path.join(result_dir, 'exp1_{}.pkl'.format(dataset)), 'wb') as f:
@@ -202,10 +224,16 @@ def main(argv=None):
                     help="score every client's local model each round on the test / validation rows")
     ap.add_argument('--local-eval', default=None, choices=['global', 'own', 'both'],
                     help="score the round's global model / every client's own model on each client's own rows")
+    ap.add_argument('--participation', type=float, default=None, metavar='F',
+                    help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
+                         'Applies to the FedAvg and FedProx calls only, which then run with parallel clients '
+                         'whatever --mode says; the other algorithms are unchanged')
+    ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
+                    help='seed of the participation sampler (a private generator; with --participation)')
     a = ap.parse_args(argv)
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
               a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval,
-              local_eval=a.local_eval)
+              local_eval=a.local_eval, participation=a.participation, sample_seed=a.sample_seed)
     for k, name in enumerate(NAMES):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

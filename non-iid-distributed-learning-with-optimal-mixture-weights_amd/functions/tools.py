@@ -50,6 +50,21 @@ Keyword-only extensions (not in the reference):
   clients into one and raises a ValueError.  Nothing is drawn from any generator and the
   returns are bitwise those of the run without the key.
 
+* ``participation`` / ``sample_seed`` (FedAvg, FedProx; needs ``clients='parallel'``) -- partial
+  client participation: only a sampled subset S_t of the clients trains in round t and is
+  aggregated, ``W_g = sum_{j in S_t} q_j W_j`` with ``q = n[S_t] / sum(n[S_t])`` folded in ascending
+  client id (fs_aggregate_sel reads the sampled rows only).  A float in (0, 1] is McMahan's
+  fraction C (``M = max(1, floor(C N + 0.5))`` clients per round), an int in [1, N] is M itself, a
+  sequence of ``round`` id arrays an explicit schedule (``functions/participation.py``).  The sampler
+  is a private generator seeded with ``sample_seed``; only the sampled clients' DataLoader passes
+  draw from the global generator (ascending client id, epoch-minor, then the test pass), as a
+  loop over the sampled clients would.  ``train_loss[t] = sum(q * losses_S)``; evaluation, the lr
+  schedule and the returns are as without the keyword, and ``participation=1.0`` is bitwise the
+  call without it.  ``stats['participants']``: the R id arrays.  Unsampled clients of a round:
+  NaN in ``stats['client_*']`` and ``stats['local_own_*']`` (``local_global_*`` covers all N).
+  FedAMW and the single-shot algorithms take no such keyword (what p means over a changing
+  subset is an open algorithm question).
+
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
 CPU path.
 
@@ -69,6 +84,7 @@ import torch
 
 from .. import dist, engine, rng
 from .. import _lib
+from . import participation as _participation
 from .._lib import FedsimError
 
 __all__ = ['FedAvg', 'FedProx', 'FedAMW', 'Centralized', 'Distributed', 'FedAMW_OneShot', 'Federation', 'RFF',
@@ -253,7 +269,7 @@ class Federation:
 
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
-                 shuffle_device=True, options=None):
+                 shuffle_device=True, options=None, participation=None, sample_seed=0):
         opts = dict(OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -272,6 +288,18 @@ class Federation:
             raise ValueError("clients must be 'sequential' or 'parallel'")
         self.chained = clients == 'sequential'
         self.rank, nranks = dist.world()
+        # partial participation: self.sched[t] = the sorted ids of the clients that train in round t
+        # (None: every client, every round -- the code path without the keyword, untouched)
+        self.sched = None
+        if participation is not None:
+            if algo not in ('fedavg', 'fedprox'):
+                raise NotImplementedError('participation is implemented for FedAvg and FedProx only')
+            if self.chained:
+                raise ValueError("participation needs clients='parallel': every sampled client starts from the "
+                                 "round's global model (clients='sequential' chains all clients)")
+            if nranks > 1:
+                raise NotImplementedError('participation over more than one torch.distributed rank is not implemented')
+            self.sched = _participation.make_schedule(len(y_train), int(round), participation, sample_seed)
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -340,6 +368,24 @@ class Federation:
         else:
             self.agg = engine.Aggregator(len(mine), C, ld, dev)
         self.loss_hist = torch.empty(R, len(mine), dtype=torch.float64, device=dev)
+        if self.sched is not None:
+            # the whole schedule goes to the device once, before round 0: per round the sampled ids
+            # ascending (the aggregate's fold order) and in dispatch order (LPT over the sample:
+            # steps descending, stable), and q = n[S] / sum(n[S]) as tools.py:333 restricted to S.
+            # [R][max M], a round reads its first M_t entries; held for the whole run (the
+            # launches read them asynchronously).  Unsampled clients' losses stay NaN.
+            self.loss_hist.fill_(float('nan'))
+            Mx = max([len(S) for S in self.sched] + [1])
+            sel_h, ord_h = np.zeros((R, Mx), np.int32), np.zeros((R, Mx), np.int32)
+            q_h = torch.zeros(R, Mx, dtype=torch.float32)
+            self.q_host = []
+            for t, S in enumerate(self.sched):
+                q = torch.tensor(ns[S] / sum(ns[S]), dtype=torch.float32)
+                self.q_host.append(q)
+                sel_h[t, :len(S)], ord_h[t, :len(S)], q_h[t, :len(S)] = S, self.trainer.sel_order(S), q
+            self.sel_dev = torch.from_numpy(sel_h).to(dev)
+            self.sel_order_dev = torch.from_numpy(ord_h).to(dev)
+            self.q_dev = q_h.to(dev)
         self.eval_hist = torch.empty(R, 2, dtype=torch.float64, device=dev)
         self.W_hist = torch.empty(R, C, ld, device=dev) if (stats is not None and stats.get('trace')) else None
         # stats['client_eval']: every local model of the round scored on the test and / or the
@@ -373,7 +419,7 @@ class Federation:
         # use them, so consecutive rounds run with no cross-stream wait between them.  FedAMW
         # keeps per-round shuffles (its validation shuffles are double-buffered per round).
         self.chunk = 1
-        if self.mixture is None and shuffle_device:
+        if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
             if self.chunk > 1:
                 self.plan.set_chunk(self.chunk)
@@ -390,6 +436,13 @@ class Federation:
         order: train passes client-major, then validation passes, then the test pass), replay
         the training shuffles into the plan's slot t % 2 (on its side stream) and enqueue the validation shuffles (FedAMW) on the side stream."""
         N, E = self.N, self.E
+        if self.sched is not None:
+            # only the sampled clients' passes draw (ascending client id, epoch-minor), then the
+            # test pass: M_t * E + n_val_pass + 1 passes
+            S = self.sched[t]
+            seeds = rng.draw_pass_seeds(len(S) * E + self.n_val_pass + 1)
+            self.plan.shuffle_subset(seeds[:len(S) * E], S, t)
+            return
         seeds = rng.draw_pass_seeds(N * E + self.n_val_pass + 1)
         self.plan.shuffle(seeds[:N * E].reshape(N, E)[self.mine].reshape(-1), t)
         if self.mixture is not None:
@@ -431,7 +484,21 @@ class Federation:
             ev.append((name, a, b))
             return out
 
-        timed('train', lambda: self.plan.round(t, self.lr, P[0]))
+        if self.sched is not None:
+            M = len(self.sched[t])
+
+            def plan_round(phases):
+                self.plan.round_subset(t, self.lr, phases, self.sel_dev[t], self.sel_order_dev[t], self.q_dev[t], M)
+        else:
+            def plan_round(phases):
+                self.plan.round(t, self.lr, phases)
+        timed('train', lambda: plan_round(P[0]))
+        # (under participation the two evaluations of the clients' OWN models below still score all
+        # N rows of W_out -- stale rows of clients that sat the round out, zeros before a client's
+        # first round -- and results() masks the unsampled ones to NaN: both evaluators walk the
+        # clients x params buffer by position.  At 10 % participation that is 10 x the work this
+        # stats path needs; scoring the sampled rows only would take an index table in
+        # fs_mix_z / fs_eval_clients, not done here.)
         if 'test' in self.client_eval:
             ce, hist, _ = self.client_eval['test']
             timed('client_eval_test', lambda: ce.run(self.trainer.W_out, len(self.mine), hist[t]))
@@ -486,7 +553,7 @@ class Federation:
             dist.allreduce_sum_(self.W_g)
             self.plan.round(t, self.lr, P[2])
         else:
-            self.plan.round(t, self.lr, P[1] | P[2])
+            plan_round(P[1] | P[2])
         if 'global' in self.local_hist:     # the W_g that test_loss[t] scores (read only: a deferred test
             # evaluation, which reads it in round t+1's training launch, is not disturbed)
             timed('local_eval_global', lambda: self.local_eval.run(self.W_g, 0, self.local_hist['global'][t]))
@@ -498,6 +565,18 @@ class Federation:
                 self._prepare_upto(t + 2 * self.chunk)
         elif self.t < self.R and not early:
             self._prepare_upto(self.t + 1)
+
+    def _mask_unsampled(self, hist):
+        """hist [R, N, 2] of every client's OWN model per round: under partial participation a
+        copy with NaN for the clients that did not train in a round (their W_out rows are stale)."""
+        if self.sched is None:
+            return hist
+        keep = torch.zeros(hist.shape[0], hist.shape[1], dtype=torch.bool)
+        for t, S in enumerate(self.sched):
+            keep[t, torch.from_numpy(S)] = True
+        hist = hist.clone()
+        hist[~keep.to(hist.device)] = float('nan')
+        return hist
 
     def results(self):
         """Single host sync: (train_loss, test_loss, test_acc) CPU float32 tensors."""
@@ -517,7 +596,10 @@ class Federation:
         train_loss, test_loss, test_acc = torch.zeros(self.R), torch.zeros(self.R), torch.zeros(self.R)
         for t in range(R):
             pt = ph[t] if ph is not None else self.p_all
-            train_loss[t] = torch.sum(pt * torch.tensor([float(v) for v in lh[t]]))   # tools.py:344 / 434
+            if self.sched is not None:     # the sampled clients' weights and losses, ascending client id
+                train_loss[t] = torch.sum(self.q_host[t] * torch.tensor([float(v) for v in lh[t][self.sched[t]]]))
+            else:
+                train_loss[t] = torch.sum(pt * torch.tensor([float(v) for v in lh[t]]))   # tools.py:344 / 434
             test_loss[t], test_acc[t] = float(ev[t, 0]), float(ev[t, 1])
             if self.verbose and self.rank == 0:
                 print('Test loss: {}, \t Test Acc: {}'.format(float(ev[t, 0]), float(ev[t, 1])))
@@ -529,12 +611,17 @@ class Federation:
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
+            if self.sched is not None:
+                self.stats['participants'] = [S.copy() for S in self.sched]
             for which, (_, hist, _) in self.client_eval.items():
+                hist = self._mask_unsampled(hist)
                 if self.sharded:      # as loss_hist: rank-major rows, then the caller's client order
                     hist = dist.allgather_rows(hist.permute(1, 0, 2).contiguous(), [len(s) for s in self.shards])
                     hist = hist[self.inv].permute(1, 0, 2)
                 _client_eval_stats(self.stats, which, hist)
             for which, hist in self.local_hist.items():
+                if which == 'own':
+                    hist = self._mask_unsampled(hist)
                 if self.sharded:      # each rank scored its own shard: gather, then the caller's client order
                     hist = dist.allgather_rows(hist.permute(1, 0, 2).contiguous(), [len(s) for s in self.shards])
                     hist = hist[self.inv].permute(1, 0, 2)
@@ -542,8 +629,9 @@ class Federation:
         return train_loss, test_loss, test_acc
 
 
-def _run(algo, *args, stats=None, verbose=True, options=None):
-    fed = Federation(algo, *args, stats=stats, verbose=verbose, options=options)
+def _run(algo, *args, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    fed = Federation(algo, *args, stats=stats, verbose=verbose, options=options, participation=participation,
+                     sample_seed=sample_seed)
     for _ in range(fed.R):
         fed.round()
     return fed.results()
@@ -551,20 +639,22 @@ def _run(algo, *args, stats=None, verbose=True, options=None):
 
 def FedAvg(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *,
-           clients='sequential', stats=None, verbose=True, options=None):
-    """tools.py:329-353.  ``options``: launch-scheduling options (``OPTIONS``)."""
+           clients='sequential', stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """tools.py:329-353.  ``options``: launch-scheduling options (``OPTIONS``).  ``participation`` /
+    ``sample_seed``: partial client participation (module docstring; needs ``clients='parallel'``)."""
     return _run('fedavg', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
                 prox, mu, lambda_reg_if, lambda_reg, round, None, clients, stats=stats, verbose=verbose,
-                options=options)
+                options=options, participation=participation, sample_seed=sample_seed)
 
 
 def FedProx(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
             batch_size=32, prox=True, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *,
-            clients='sequential', stats=None, verbose=True, options=None):
-    """tools.py:356-380 (FedAvg with the proximal term on by default)."""
+            clients='sequential', stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """tools.py:356-380 (FedAvg with the proximal term on by default).  ``participation`` /
+    ``sample_seed`` as FedAvg's."""
     return _run('fedprox', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
                 prox, mu, lambda_reg_if, lambda_reg, round, None, clients, stats=stats, verbose=verbose,
-                options=options)
+                options=options, participation=participation, sample_seed=sample_seed)
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
