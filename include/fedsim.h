@@ -40,7 +40,7 @@ extern "C" {
 #define FS_EHIP (-2)
 #define FS_EUNSUPPORTED (-3)
 
-#define FS_ABI_VERSION 22
+#define FS_ABI_VERSION 23
 
 /* ABI version and the last error message of the calling thread. */
 int fs_abi_version(void);
@@ -318,6 +318,34 @@ int fs_aggregate(const float* d_W_all, int64_t stride, const float* d_p, int N, 
  * ------------------------------------------------------------------------- */
 int fs_aggregate_sel(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
                      int64_t len, float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * (ABI 23) FedNova's scaled fold (tools.py:383-410) over M rows of the clients x params buffer,
+ * in k order, every operation rounded separately.  W[j] = d_W_all + j*stride, len floats; d_sel
+ * [M] int32 row ids (valid rows: the caller's contract), or NULL for rows 0..M-1; d_q [M].
+ *   mode FS_NOVA_REFERENCE  the reference's lines (tools.py:401-405), which scale the WEIGHTS:
+ *       d_W_bar = fl(W[sel_0]*s0) + sum_{k>=1} fl( fl( fl(q_k*W[sel_k]) * te ) / d_b[k] )
+ *     with the correctly rounded IEEE quotient.  Bitwise the reference's fold for
+ *     s0 = f32(f64(p_0)*Tau_eff/Tau_0), te = f32(Tau_eff), d_b[k] = f32(Tau_k), q = p.  s0 belongs
+ *     to the fold's first row only (not to a chunk's first row); d_b[0] is not read.  For unequal
+ *     client sizes these coefficients sum to N * sum_j p_j^2 > 1, not to 1.
+ *   mode FS_NOVA_UPDATES    normalised averaging of the UPDATES (Wang et al. 2020):
+ *       d_W_bar = fl( base + sum_k fl( q_k * fl(W[sel_k] - base) ) ),  base = d_W_base [len].
+ *     d_W_base may be d_W_bar itself: every position's base is read before that position is
+ *     written, by the same workgroup.  d_b, te and s0 are not read.
+ * The first term of any range is the term itself, not 0 + term.  Regimes are fs_aggregate's,
+ * chosen by M with the same `chunks`, d_ws and ws_floats: for M < 16 or chunks == 1 the exact
+ * left fold, else the same sub-ranges / chunks and stage-2 tree.  Mode 1 with te = 1, d_b == 1,
+ * s0 = q_0 is bitwise fs_aggregate / fs_aggregate_sel.  Rows outside d_sel are never read.  No
+ * atomics, no cross-workgroup wait, no allocation; asynchronous on `stream`.
+ * FS_EINVAL for M < 1, len / stride not multiples of 4, a null pointer the mode needs, or a mode
+ * other than 1 or 2.
+ * ------------------------------------------------------------------------- */
+#define FS_NOVA_REFERENCE 1
+#define FS_NOVA_UPDATES   2
+int fs_aggregate_nova(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q,
+                      const float* d_b, float te, float s0, int mode, const float* d_W_base, int M, int64_t len,
+                      float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Test evaluation.  Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
@@ -700,6 +728,18 @@ int fs_plan_eval_blocks(const fs_plan* plan);
 int fs_plan_shuffle_subset(fs_plan* plan, const int64_t* h_seeds, const int32_t* h_sel, int M, int t);
 int fs_plan_round_subset(fs_plan* plan, int t, float lr, int phases, const int32_t* d_sel,
                          const int32_t* d_sel_order, const float* d_q, int M, void* stream);
+
+/* (ABI 23) The aggregation rule of this plan's AGGREGATE phase.  mode 0 (the default) is the plain
+ * aggregate; FS_NOVA_REFERENCE / FS_NOVA_UPDATES make AGGREGATE launch fs_aggregate_nova in that
+ * mode instead of fs_aggregate / fs_aggregate_sel, with d_q = the round's weights (d_p, the
+ * override, or the subset call's d_q), d_sel = the subset's ids or NULL, d_W_base = d_W_g (mode 2
+ * updates the round-start model in place) and the same finaliser handling.  Host state: the next
+ * fs_plan_round / fs_plan_round_subset whose phases include FS_PHASE_AGGREGATE reads it when it
+ * enqueues, so it may change between rounds (a sampled round's d_b / te / s0).  d_b [N, or M of a
+ * subset round] is a device array read asynchronously by those launches (mode 1 only).  Nothing
+ * else about the plan changes.  FS_EINVAL for mode 2 on a chained plan (a chained client's
+ * W_j - W_g contains its predecessors' work), mode 1 with a null d_b, or another mode. */
+int fs_plan_set_nova(fs_plan* plan, int mode, const float* d_b, float te, float s0);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

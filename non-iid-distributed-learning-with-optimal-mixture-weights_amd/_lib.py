@@ -40,6 +40,9 @@ _SIGS = {
                                C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'fs_aggregate_sel': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                    C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'fs_aggregate_nova': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                    C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_int, C.c_void_p]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -87,6 +90,7 @@ _SIGS = {
     'fs_plan_shuffle_subset': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     'fs_plan_round_subset': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p]),
+    'fs_plan_set_nova': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float]),
     'fs_local_train_last_kernel': (C.c_int, []),
     'fs_plan_set_shuffle_chunk': (C.c_int, [C.c_void_p, C.c_int]),
     'fs_plan_shuffle_flush': (C.c_int, [C.c_void_p]),
@@ -98,9 +102,10 @@ _SIGS = {
 }
 
 EXPORTS = tuple(_SIGS)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
+NOVA_REFERENCE, NOVA_UPDATES = 1, 2   # fs_aggregate_nova / fs_plan_set_nova modes (ABI 23)
 G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
 G_TEAMS = 512            # fs_local_train_plan: G | G_TEAMS = the team form at width G (ABI 13)
 LT_KERNELS = {1: 'single', 2: 'split', 3: 'dbuf', 4: 'pair', 5: 'pipe', 6: 'teams', 7: 'mb',
@@ -325,6 +330,7 @@ KERNEL_SOURCES = {
     'local_train_mse': ('local_train_mse.hip', 'mse_rows.h', 'common.h'),
     'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),
     'z_eval': ('z_eval.hip', 'common.h'),
+    'aggregate_nova': ('aggregate_nova.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
 }
 
 

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void aggregate_kernel(const float* __restrict_
 // ... in order, then thread 0 of the position folding the FP_SUB sums in order (a fixed tree:
 // the same bits every run).  One thread per position walking all K partials put only len4 / 256
 // workgroups on the chip (config 4: 20 CUs, 20 us for 5 MB of partials).
-constexpr int FP_SUB = 8, FP_POS = 256 / FP_SUB;
+constexpr int FP_SUB = AG_FP_SUB, FP_POS = 256 / FP_SUB;
 
 __global__ __launch_bounds__(256) void fold_partials_kernel(const float* __restrict__ part, int K, int64_t len4,
                                                            float* __restrict__ out) {

@@ -1,4 +1,5 @@
-// What fs_aggregate (aggregate.hip) and fs_aggregate_sel (aggregate_sel.hip) share: the regime
+// What fs_aggregate (aggregate.hip), fs_aggregate_sel (aggregate_sel.hip) and fs_aggregate_nova
+// (aggregate_nova.hip) share: the regime
 // threshold, the sub-range and chunk rules and the stage-2 fold, so the gathered fold takes the
 // same path as the contiguous one at the same client count -- its contract is bitwise equality.
 #pragma once
@@ -7,6 +8,7 @@
 namespace fs {
 
 constexpr int AG_ONE_MAX_N = 512;   // clients up to which chunks <= 0 is the one-launch form
+constexpr int AG_FP_SUB = 8;        // threads per float4 position of the stage-2 tree (fold_partials_launch)
 
 int one_launch_sub(int N);          // sub-ranges per float4 position of the one-launch form
 // chunks and clients per chunk of the two-stage form (chunks <= 0: by the shape; clamped to the
@@ -19,5 +21,11 @@ void fold_partials_launch(const float* d_part, int K, int64_t len4, float* d_out
 int aggregate_sel_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
                          int64_t len, float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks,
                          const EvalFinalize* fin, hipStream_t st);
+
+// fs_aggregate_nova (aggregate_nova.hip) with an optional finaliser, as the two above
+int aggregate_nova_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q,
+                          const float* d_b, float te, float s0, int mode, const float* d_W_base, int M, int64_t len,
+                          float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, const EvalFinalize* fin,
+                          hipStream_t st);
 
 }  // namespace fs

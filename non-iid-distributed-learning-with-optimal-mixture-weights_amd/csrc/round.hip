@@ -25,6 +25,9 @@
 // at the usual offsets), the plan's training form is launched over the M clients through its
 // `order` table on the unchanged W_out / loss history, and the aggregate gathers the M sampled
 // rows (fs_aggregate_sel).  Rows of W_out and the history outside the sample are not touched.
+//
+// FedNova (ABI 23, fs_plan_set_nova): AGGREGATE of either kind of round launches fs_aggregate_nova
+// (aggregate_nova.hip) instead, with the round's weights as q and d_W_g as the base it updates.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -157,6 +160,10 @@ struct fs_plan {
   int eval_pending = -1;              // round whose evaluation rides on the next TRAIN launch
   int fin_pending = -1;               // round whose fused evaluation awaits its finaliser (it rides
                                       // on the next AGGREGATE launch, fs_plan_round)
+  // fs_plan_set_nova: AGGREGATE is fs_aggregate_nova in this mode (0: the plain aggregate)
+  int nova_mode = 0;
+  const float* nova_b = nullptr;
+  float nova_te = 1.f, nova_s0 = 1.f;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -788,10 +795,18 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
     const fs::EvalFinalize fin = fin_of(p->fin_pending);
     const bool with_fin = p->fin_pending >= 0;
     p->fin_pending = -1;
-    const int rc = sub ? fs::aggregate_sel_launch(d.d_W_out, len, sub->sel, pw, sub->M, len, d.d_W_g, d.d_agg_ws,
-                                                  d.agg_ws_floats, d.agg_chunks, with_fin ? &fin : nullptr, st)
-                       : fs::aggregate_launch(d.d_W_out, len, pw, d.N, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats,
-                                              d.agg_chunks, with_fin ? &fin : nullptr, st);
+    const int32_t* sel = sub ? sub->sel : nullptr;
+    const int M = sub ? sub->M : d.N;
+    const fs::EvalFinalize* f = with_fin ? &fin : nullptr;
+    int rc;
+    if (p->nova_mode)
+      rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
+                                     M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
+    else if (sub)
+      rc = fs::aggregate_sel_launch(d.d_W_out, len, sel, pw, M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats,
+                                    d.agg_chunks, f, st);
+    else
+      rc = fs::aggregate_launch(d.d_W_out, len, pw, M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
     if (rc != FS_OK) return rc;
   }
   // (a finaliser still pending here is launched by the next fs_plan_round call -- any call that
@@ -806,6 +821,22 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
     const int rc = plan_eval(d, t, st);
     if (rc != FS_OK) return rc;
   }
+  return FS_OK;
+}
+
+// ABI 23: the aggregation rule of the AGGREGATE phases enqueued from now on (host state, read
+// when a round call enqueues): 0 the plain aggregate, else fs_aggregate_nova in that mode with
+// q = the round's weights, base = d_W_g (mode 2, in place).  d_b is read by those launches.
+extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te, float s0) {
+  FS_REQUIRE(p, "bad arguments");
+  FS_REQUIRE(mode == 0 || mode == FS_NOVA_REFERENCE || mode == FS_NOVA_UPDATES, "mode must be 0, 1 or 2");
+  FS_REQUIRE(mode != FS_NOVA_REFERENCE || d_b, "mode 1 needs d_b");
+  FS_REQUIRE(!(mode == FS_NOVA_UPDATES && p->d.chained),
+             "mode 2 needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  p->nova_mode = mode;
+  p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
+  p->nova_te = te;
+  p->nova_s0 = s0;
   return FS_OK;
 }
 

@@ -398,6 +398,17 @@ class RoundPlan:
                                                    _lib.ptr(sel_order), _lib.ptr(q), M, _lib.stream_ptr()),
                    'fs_plan_round_subset')
 
+    def set_nova(self, mode, b=None, te=1.0, s0=1.0):
+        """fs_plan_set_nova: the rule of the AGGREGATE phases enqueued from now on -- 0 the plain
+        aggregate, 1 (``_lib.NOVA_REFERENCE``) / 2 (``_lib.NOVA_UPDATES``) fs_aggregate_nova with the
+        round's weights as ``q`` and ``W_g`` as the base.  ``b`` (mode 1): a float32 device tensor the
+        launches read asynchronously; the plan keeps the last one alive."""
+        if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()):
+            raise ValueError('set_nova: b must be a contiguous float32 device tensor')
+        _lib.check(_lib.lib().fs_plan_set_nova(self._h, int(mode), None if b is None else _lib.ptr(b), float(te),
+                                               float(s0)), 'fs_plan_set_nova')
+        self._nova_b = b
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -450,6 +461,38 @@ class Aggregator:
         _lib.check(_lib.lib().fs_aggregate_sel(_lib.ptr(W_all), self.len, _lib.ptr(sel), _lib.ptr(q), M, self.len,
                                                _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
                                                _lib.stream_ptr()), 'fs_aggregate_sel')
+        return out
+
+
+    def run_nova(self, W_all, q, out, mode, b=None, te=1.0, s0=1.0, base=None, sel=None, check=True):
+        """fs_aggregate_nova: FedNova's scaled fold over the rows ``sel`` of ``W_all`` (None: rows
+        0..len(q)-1) in k order, in the regimes of ``run`` at len(q) clients.  mode 1
+        (``_lib.NOVA_REFERENCE``): ``out = W[sel_0]*s0 + sum_{k>=1} ((q_k*W[sel_k])*te)/b_k``, the
+        reference's lines; mode 2 (``_lib.NOVA_UPDATES``): ``out = base + sum_k q_k*(W[sel_k] - base)``,
+        where ``base`` may be ``out``.  ``check`` as in ``run_sel``."""
+        M = int(q.numel())
+
+        def f32(x):
+            return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if not (f32(q) and M >= 1 and (b is None or (f32(b) and b.numel() == M))
+                and (base is None or (f32(base) and base.numel() >= self.len))):
+            raise ValueError('run_nova: q, b (float32, equal non-zero length) and base (float32, len) must be '
+                             'contiguous device tensors')
+        if sel is not None:
+            if not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == M):
+                raise ValueError('run_nova: sel must be a contiguous int32 device tensor as long as q')
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('run_nova: q is longer than W_all has rows')
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_nova: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_nova(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                                _lib.ptr(q), None if b is None else _lib.ptr(b), float(te), float(s0),
+                                                int(mode), None if base is None else _lib.ptr(base), M, self.len,
+                                                _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
+                                                _lib.stream_ptr()), 'fs_aggregate_nova')
         return out
 
 

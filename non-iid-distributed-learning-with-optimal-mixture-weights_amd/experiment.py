@@ -51,6 +51,9 @@ from .functions.optimal_parameters import get_parameter
 from . import engine
 
 NAMES = ['CL', 'DL', 'FedAMW_OneShot', 'FedAvg', 'FedProx', 'FedAMW']
+# exp.py:124 leaves its FedNova call commented out: it runs only when ``algos`` names it, and its
+# rows are then appended after the six above (the default result layout is unchanged)
+EXTRA = ['FedNova']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -93,30 +96,34 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
         raise ValueError("local_eval must be None, 'global', 'own' or 'both'")
+    unknown = [n for n in algos if n not in NAMES + EXTRA]
+    if unknown:
+        raise ValueError('unknown algorithm(s) %s (known: %s)' % (', '.join(unknown), ', '.join(NAMES + EXTRA)))
+    names = list(NAMES) + [n for n in EXTRA if n in algos]
     lwant = {None: (), 'both': ('global', 'own')}.get(local_eval, (local_eval,))
     want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
-    cev = {'client_%s_%s' % (w, m): [None] * len(NAMES) for w in want for m in ('loss', 'acc')}
-    cev.update({'local_%s_%s' % (w, m): [None] * len(NAMES) for w in lwant for m in ('loss', 'acc')})
+    cev = {'client_%s_%s' % (w, m): [None] * len(names) for w in want for m in ('loss', 'acc')}
+    cev.update({'local_%s_%s' % (w, m): [None] * len(names) for w in lwant for m in ('loss', 'acc')})
     if 'global' in lwant:
-        cev['global_objective'] = [None] * len(NAMES)
+        cev['global_objective'] = [None] * len(names)
     torch.manual_seed(100)
     np.random.seed(100)
     P = get_parameter(dataset)
     task, C, k_par = P['task_type'], P['num_classes'], P['kernel_par']
     lr, mu, lam = P['lr'], P['lambda_prox'], P['lambda_reg']
     lr_p, lr_p_os, lam_os = P.get('lr_p', 1e-3), P.get('lr_p_os', 1e-3), P.get('lambda_reg_os', P['lambda_reg'])
-    train_mat = np.empty((6, Round, n_repeats))
-    error_mat = np.empty((6, Round, n_repeats))
-    acc_mat = np.empty((6, Round, n_repeats))
+    train_mat = np.empty((len(names), Round, n_repeats))
+    error_mat = np.empty((len(names), Round, n_repeats))
+    acc_mat = np.empty((len(names), Round, n_repeats))
     hete_mat = np.empty(n_repeats)
     timing = {}
-    # partial participation (FedAvg and FedProx only, which then run with parallel clients):
+    # partial participation (FedAvg, FedProx and FedNova only, which then run with parallel clients):
     # participants[k][repeat] = the R sampled id arrays of algorithm k's call
-    participants = [None] * len(NAMES)
+    participants = [None] * len(names)
 
     def keep_participants(name, st):
         if participation is not None:
-            k = NAMES.index(name)
+            k = names.index(name)
             participants[k] = (participants[k] or []) + [st['participants']]
 
     for t in range(n_repeats):
@@ -144,13 +151,13 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
                 st['local_eval'] = lwant
             st = st or None
             if st is not None:
-                calls.append((NAMES.index(name), st))
+                calls.append((names.index(name), st))
             return st
 
         calls = []
 
         # exp.py:116-130, positional as the reference calls them; skipped algorithms leave NaN rows
-        for k in range(6):
+        for k in range(len(names)):
             train_mat[k, :, t] = error_mat[k, :, t] = acc_mat[k, :, t] = np.nan
         if 'CL' in algos:
             r = timed('CL', lambda: tools.Centralized(*a, task, C, D, lr, local_epoch * Round, batch_size, False, 0,
@@ -187,6 +194,15 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
                                                      False, 0, True, lam, Round, lr_p, stats=ce('FedAMW', True),
                                                      **par))
             train_mat[5, :, t], error_mat[5, :, t], acc_mat[5, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        if 'FedNova' in algos:
+            # exp.py:124's arguments; the reference form (tools.FedNova's variant='reference')
+            st = ce('FedNova', False)
+            if participation is not None:
+                st = st or {}
+            r = timed('FedNova', lambda: tools.FedNova(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False, 0,
+                                                       Round, stats=st, **fpar))
+            keep_participants('FedNova', st)
+            train_mat[6, :, t], error_mat[6, :, t], acc_mat[6, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -194,7 +210,7 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
                         cev[key][k] = []
                     cev[key][k].append(st[key].numpy())
     data_ = {'epochs': Round, 'train_loss': train_mat, 'test_loss': error_mat, 'test_acc': acc_mat,
-             'heterogeneity': hete_mat, 'name': list(NAMES), 'seconds': {k: list(v) for k, v in timing.items()}}
+             'heterogeneity': hete_mat, 'name': names, 'seconds': {k: list(v) for k, v in timing.items()}}
     data_.update(cev)
     if participation is not None:
         data_['participants'] = participants
@@ -218,7 +234,8 @@ def main(argv=None):
     ap.add_argument('--data-dir', default='../FedAMW/datasets/')
     ap.add_argument('--result-dir', default='./results')
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
-    ap.add_argument('--algos', default=','.join(NAMES))
+    ap.add_argument('--algos', default=','.join(NAMES),
+                    help='comma-separated; FedNova (exp.py:124, commented out there) runs only when named here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -226,7 +243,7 @@ def main(argv=None):
                     help="score the round's global model / every client's own model on each client's own rows")
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
-                         'Applies to the FedAvg and FedProx calls only, which then run with parallel clients '
+                         'Applies to the FedAvg, FedProx and FedNova calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')
@@ -234,7 +251,7 @@ def main(argv=None):
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
               a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval,
               local_eval=a.local_eval, participation=a.participation, sample_seed=a.sample_seed)
-    for k, name in enumerate(NAMES):
+    for k, name in enumerate(out['name']):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})
     return out

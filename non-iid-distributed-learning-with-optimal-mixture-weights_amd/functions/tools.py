@@ -1,7 +1,7 @@
-"""Drop-in FedAvg / FedProx / FedAMW on MI355X.
+"""Drop-in FedAvg / FedProx / FedNova / FedAMW on MI355X.
 
 Same names, positional signatures, defaults and return values as the reference
-(/root/reference/functions/tools.py:329, 356, 413):
+(/root/reference/functions/tools.py:329, 356, 383, 413):
 
     train_loss, test_loss, test_acc = FedAvg(X_train, y_train, X_test, y_test, type,
                                              num_classes, D, lr, epoch, batch_size, prox,
@@ -50,7 +50,7 @@ Keyword-only extensions (not in the reference):
   clients into one and raises a ValueError.  Nothing is drawn from any generator and the
   returns are bitwise those of the run without the key.
 
-* ``participation`` / ``sample_seed`` (FedAvg, FedProx; needs ``clients='parallel'``) -- partial
+* ``participation`` / ``sample_seed`` (FedAvg, FedProx, FedNova; needs ``clients='parallel'``) -- partial
   client participation: only a sampled subset S_t of the clients trains in round t and is
   aggregated, ``W_g = sum_{j in S_t} q_j W_j`` with ``q = n[S_t] / sum(n[S_t])`` folded in ascending
   client id (fs_aggregate_sel reads the sampled rows only).  A float in (0, 1] is McMahan's
@@ -64,6 +64,9 @@ Keyword-only extensions (not in the reference):
   NaN in ``stats['client_*']`` and ``stats['local_own_*']`` (``local_global_*`` covers all N).
   FedAMW and the single-shot algorithms take no such keyword (what p means over a changing
   subset is an open algorithm question).
+* ``variant`` (FedNova) -- ``'reference'`` (default): the reference's aggregate, tools.py:401-405,
+  bitwise its fold (fs_aggregate_nova mode 1); ``'updates'``: Wang et al.'s normalised averaging
+  of the clients' updates (mode 2; needs ``clients='parallel'``).  See ``FedNova`` and DESIGN 4.2.2.
 
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
 CPU path.
@@ -263,13 +266,52 @@ def _local_eval_once(stats, which, le, W, stride):
 OPTIONS = {'shuffle_chunk': 8, 'defer_eval': True, 'fedamw_shuffle': 'early'}
 
 
+NOVA_VARIANTS = ('reference', 'updates')
+
+
+def _check_nova(variant, clients):
+    """FedNova's keyword checks (host only: before any device is touched)."""
+    if variant not in NOVA_VARIANTS:
+        raise ValueError("variant must be 'reference' or 'updates'")
+    if variant == 'updates' and clients != 'parallel':
+        raise ValueError("variant='updates' needs clients='parallel': a chained client's W_j - W_g contains its "
+                         "predecessors' work")
+
+
+def nova_reference_coefficients(ns, epoch, batch_size):
+    """The host scalars of tools.py:387-389 / 403-405 over the clients ``ns`` (all of them, or a
+    round's sample in ascending id), by the reference's own torch expressions: p float32,
+    Tau = n*E/B float64, Tau_eff = sum(Tau*p) float64; the weights tensors are float32, so
+    line 403's factor reaches them as s0 = f32(f64(p_0)*Tau_eff/Tau_0) and line 405's as
+    te = f32(Tau_eff), b_j = f32(Tau_j).  Returns (p, b, te, s0)."""
+    ns = np.asarray(ns)
+    p = torch.tensor(ns / sum(ns), dtype=torch.float32)
+    Tau = torch.tensor(ns * epoch / batch_size)
+    Tau_eff = torch.sum(Tau * p)
+    s0 = (p[0] * Tau_eff / Tau[0]).to(torch.float32)
+    return p, Tau.to(torch.float32), float(Tau_eff.to(torch.float32)), float(s0)
+
+
+def nova_update_coefficients(ns, epoch, batch_size):
+    """Wang et al.'s normalised averaging over the clients ``ns``: tau_j = E*ceil(n_j/B), the steps
+    train_loop takes; tau_eff = sum_j p_j tau_j (float64, p float32 as tools.py:387);
+    a_j = f32(p_j*tau_eff/tau_j), which sum to 1 up to rounding.  Returns (p, a)."""
+    ns = np.asarray(ns)
+    p = torch.tensor(ns / sum(ns), dtype=torch.float32)
+    tau = torch.tensor(epoch * -(-ns // batch_size), dtype=torch.float64)
+    tau_eff = torch.sum(p.to(torch.float64) * tau)
+    return p, (p.to(torch.float64) * tau_eff / tau).to(torch.float32)
+
+
 class Federation:
     """One algorithm call split into setup / rounds / results (bench.py drives the
     rounds one at a time through the same code path as the drop-ins)."""
 
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
-                 shuffle_device=True, options=None, participation=None, sample_seed=0):
+                 shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference'):
+        if algo == 'fednova':
+            _check_nova(variant, clients)
         opts = dict(OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -292,14 +334,16 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox'):
-                raise NotImplementedError('participation is implemented for FedAvg and FedProx only')
+            if algo not in ('fedavg', 'fedprox', 'fednova'):
+                raise NotImplementedError('participation is implemented for FedAvg, FedProx and FedNova only')
             if self.chained:
                 raise ValueError("participation needs clients='parallel': every sampled client starts from the "
                                  "round's global model (clients='sequential' chains all clients)")
             if nranks > 1:
                 raise NotImplementedError('participation over more than one torch.distributed rank is not implemented')
             self.sched = _participation.make_schedule(len(y_train), int(round), participation, sample_seed)
+        if algo == 'fednova' and nranks > 1:
+            raise NotImplementedError('FedNova over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -368,6 +412,19 @@ class Federation:
         else:
             self.agg = engine.Aggregator(len(mine), C, ld, dev)
         self.loss_hist = torch.empty(R, len(mine), dtype=torch.float64, device=dev)
+        # FedNova (tools.py:383-410): FedAvg's round with fs_aggregate_nova as its aggregate.
+        # 'reference': the reference's host scalars, mode 1 with q = p; 'updates': mode 2 with
+        # q = a.  train_loss keeps the plain p (tools.py:400).  Under participation the scalars are
+        # taken over each round's sample (below) and set before that round's aggregate.
+        self.nova = None
+        p_plan = self.p_mine
+        if algo == 'fednova':
+            if variant == 'reference':
+                _, b, te, s0 = nova_reference_coefficients(ns, E, B)
+                self.nova = (_lib.NOVA_REFERENCE, b.to(dev), te, s0)
+            else:
+                p_plan = nova_update_coefficients(ns, E, B)[1].to(dev)
+                self.nova = (_lib.NOVA_UPDATES, None, 1.0, 1.0)
         if self.sched is not None:
             # the whole schedule goes to the device once, before round 0: per round the sampled ids
             # ascending (the aggregate's fold order) and in dispatch order (LPT over the sample:
@@ -383,6 +440,21 @@ class Federation:
                 q = torch.tensor(ns[S] / sum(ns[S]), dtype=torch.float32)
                 self.q_host.append(q)
                 sel_h[t, :len(S)], ord_h[t, :len(S)], q_h[t, :len(S)] = S, self.trainer.sel_order(S), q
+            if self.nova is not None:
+                # per-round b / te / s0 (reference) or a in q's place (updates), uploaded once here
+                b_h = torch.ones(R, Mx, dtype=torch.float32)
+                self.nova_round = []
+                for t, S in enumerate(self.sched):
+                    if len(S) == 0:
+                        self.nova_round.append((1.0, 1.0))
+                    elif self.nova[0] == _lib.NOVA_REFERENCE:
+                        _, b, te, s0 = nova_reference_coefficients(ns[S], E, B)
+                        b_h[t, :len(S)] = b
+                        self.nova_round.append((te, s0))
+                    else:
+                        q_h[t, :len(S)] = nova_update_coefficients(ns[S], E, B)[1]
+                        self.nova_round.append((1.0, 1.0))
+                self.nova_b_dev = b_h.to(dev)
             self.sel_dev = torch.from_numpy(sel_h).to(dev)
             self.sel_order_dev = torch.from_numpy(ord_h).to(dev)
             self.q_dev = q_h.to(dev)
@@ -406,7 +478,7 @@ class Federation:
         self.side = torch.cuda.Stream(device=dev)    # FedAMW validation shuffles of round t+1 run here
         # the native round driver (csrc/round.hip): one call per round phase, training shuffles
         # replayed into a double-buffered slot on its side stream
-        self.plan = engine.RoundPlan(self.trainer, self.W_g, self.loss_hist, p=self.p_mine,
+        self.plan = engine.RoundPlan(self.trainer, self.W_g, self.loss_hist, p=p_plan,
                                      aggregator=self.agg if self.mixture is None else None,
                                      evaluator=self.evaluator, eval_hist=self.eval_hist, prox=prox, mu=mu,
                                      reg=lambda_reg_if, lam=lambda_reg, chained=self.chained,
@@ -418,6 +490,8 @@ class Federation:
         # (options['shuffle_chunk'], default 8; 1 = per round), one chunk ahead of the rounds that
         # use them, so consecutive rounds run with no cross-stream wait between them.  FedAMW
         # keeps per-round shuffles (its validation shuffles are double-buffered per round).
+        if self.nova is not None and self.sched is None:
+            self.plan.set_nova(*self.nova)
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -486,6 +560,10 @@ class Federation:
 
         if self.sched is not None:
             M = len(self.sched[t])
+
+            if self.nova is not None:
+                self.plan.set_nova(self.nova[0], self.nova_b_dev[t] if self.nova[1] is not None else None,
+                                   *self.nova_round[t])
 
             def plan_round(phases):
                 self.plan.round_subset(t, self.lr, phases, self.sel_dev[t], self.sel_order_dev[t], self.q_dev[t], M)
@@ -629,9 +707,9 @@ class Federation:
         return train_loss, test_loss, test_acc
 
 
-def _run(algo, *args, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+def _run(algo, *args, stats=None, verbose=True, options=None, participation=None, sample_seed=0, **kw):
     fed = Federation(algo, *args, stats=stats, verbose=verbose, options=options, participation=participation,
-                     sample_seed=sample_seed)
+                     sample_seed=sample_seed, **kw)
     for _ in range(fed.R):
         fed.round()
     return fed.results()
@@ -655,6 +733,24 @@ def FedProx(X_train, y_train, X_test, y_test, type='classification', num_classes
     return _run('fedprox', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
                 prox, mu, lambda_reg_if, lambda_reg, round, None, clients, stats=stats, verbose=verbose,
                 options=options, participation=participation, sample_seed=sample_seed)
+
+
+def FedNova(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *,
+            clients='sequential', variant='reference', stats=None, verbose=True, options=None, participation=None,
+            sample_seed=0):
+    """tools.py:383-410: FedAvg's round with FedNova's aggregate (fs_aggregate_nova).
+    ``variant='reference'`` reproduces the reference's lines 401-405, which scale the clients'
+    WEIGHTS by p_j*Tau_eff/Tau_j with Tau_j = n_j*E/B: for unequal client sizes those coefficients
+    sum to N*sum_j p_j^2 > 1, very likely why exp.py leaves the call commented out.
+    ``variant='updates'`` is the method of Wang et al. (2020): W_g + sum_j a_j (W_j - W_g) with
+    a_j = p_j*tau_eff/tau_j over the steps tau_j = E*ceil(n_j/B) each client really took; it needs
+    ``clients='parallel'``.  train_loss uses the plain p in both (tools.py:400).  ``participation`` /
+    ``sample_seed`` as FedAvg's, the coefficients taken over each round's sample."""
+    _check_nova(variant, clients)
+    return _run('fednova', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, clients, stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed, variant=variant)
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
