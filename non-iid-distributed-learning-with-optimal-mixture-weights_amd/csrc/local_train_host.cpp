@@ -51,13 +51,18 @@ static unsigned spin_bound(unsigned form_limit) {
 // s_sleep(1) units before a step's first poll (fs_tuning.split_poll_delay: 0 = by width, -1 =
 // none, n > 0 = n).  By width (profiles/r04/split_poll_delay_*.txt, launch ms): G = 16 (config 5)
 // 5.35-5.37 without, 5.21-5.23 at 16, 5.29-5.31 at 24, 5.45-5.49 at 48; G = 2 (config 2) no gain
-constexpr int SPLIT_PD_WIDE = 16, SPLIT_PD_NARROW = 0;
+// while every poll ran two exchange slots.  With one slot (round 12: fewer loads pace a wave's
+// polls) G = 2 gains (profiles/r12/c2_sweep*.txt, launch us): 257.6-260.3 without, 252.4 at 3,
+// 252.5 at 4, 253.1-253.2 at 5, 254.6-254.9 at 12; the two-slot parent 260-264 at every delay.
+// G = 4 likewise (config 3, FedProx, profiles/r12/c3_sweep.txt): 4,060-4,073 without -- slower than
+// the two-slot parent's 3,973-3,989 -- 3,942-3,947 at 4, 3,926-3,928 at 8, 3,913-3,916 at 16
+constexpr int SPLIT_PD_WIDE = 16, SPLIT_PD_G2 = 4;
 static int split_poll_delay(int G, bool chained) {
   const int t = tuning().split_poll_delay;
   if (t < 0) return 0;
   if (t > 0) return t;
   if (chained) return 0;                 // one group: no other group's polls to yield to
-  return G >= 8 ? SPLIT_PD_WIDE : SPLIT_PD_NARROW;
+  return G >= 4 ? SPLIT_PD_WIDE : SPLIT_PD_G2;
 }
 
 // ---- the forms' geometry -----------------------------------------------------------------------

@@ -219,8 +219,48 @@ __device__ __forceinline__ int zp_off_mb(int r, int c) {
 //             lane 16 lg + 4 q + j, register e = grad[4 cb + j][16 q + 4 lg + e] -- wr's own layout
 // Same steps, hand-off, softmax and schedule as the 16x16x4 instances; the products are summed in
 // another order (within the fp32 tolerance of the oracle, not bitwise the other forms).
-template <int RT, int G, bool PROX, int EARLY, int TEAMS, int WAVES = SP_WAVES, int TPWK = SP_TPW, int MBK = 0>
+// Exchange slots per hand-off thread (round 12).  Thread t owns the values t + XT m, m < M, and every
+// slot is compiled code that runs each step: its publish store, its G sc1 loads per poll, the tag
+// compares, the sum.  M used to come from the padded logit count (NR * 16 + 2 = 514 at RT = 2: two
+// slots for 512 threads), but C <= 15 classes exchange at most NR * 15 + 2 = 482 values and an mb
+// instance of MBK < 4 class blocks at most NR * 4 MBK + 2.  So the instances are compiled for
+// C <= SP_C1, and C = 16 runs instances of its own, named by SP_MBK_C16 in the kernel's last
+// template argument (launch_split_k) and compiled only where their slot count differs.  (A flag
+// in an argument the instances already have, so every C <= 15 instance keeps its name; and the
+// kernel's body stays in the kernel: as a device function shared by two kernels it compiled to the
+// same step at config 2, but the late instance at G = 8 lost its staggered pre-forward waits to one
+// vmcnt(0) and ran 597 -> 625 us at config 2's shape, profiles/r12/c2_g8_sweep.txt.)
+constexpr int SP_C1 = 15;
+constexpr int SP_MBK_C16 = 8;
+template <int RT, int G, int XT, int MBK, bool C16>
+constexpr int split_slots() {
+  constexpr int cmax = (MBK > 0 && MBK < 4) ? 4 * MBK : (C16 ? 16 : SP_C1);
+  constexpr int nv = RT * 16 * cmax + 2;
+  return ((G >= 8 && nv > 512 ? 512 : nv) + XT - 1) / XT;   // (G >= 8: NR * C + 2 <= 512, split_fits)
+}
+// max over the 16 lanes of a DPP row, one v_max_f32_dpp per level, as the quad p-solver's row16_max
+// (hipcc's fmaxf over a DPP move costs a move, a canonicalising max and the max per level).  Inputs
+// are finite or -inf, so the max is the same bits in any order.
+__device__ __forceinline__ float sp_row16_max(float x) {
+  float r;
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "=&v"(r)
+      : "v"(x));
+  return r;
+}
+
+template <int RT, int G, bool PROX, int EARLY, int TEAMS, int WAVES = SP_WAVES, int TPWK = SP_TPW, int MBKC = 0>
 __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTParams P, SplitWS X) {
+  constexpr int MBK = MBKC & 7;
+  constexpr bool C16 = (MBKC & SP_MBK_C16) != 0;
   static_assert(TEAMS == 1 || TEAMS == 2, "teams");
   static_assert(WAVES == SP_WAVES || (WAVES == 4 && TEAMS == 1), "waves");
   static_assert(MBK >= 0 && MBK <= 4 && (MBK == 0 || TEAMS == 1), "mb");
@@ -235,8 +275,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
   constexpr int NZS = NR * NCS;
   constexpr int TPW = TPWK;
   constexpr int XT = NTH;                         // threads running the hand-off
-  // exchanged values per hand-off thread: NR*C logits + 2 norms (G >= 8: NR*C + 2 <= 512)
-  constexpr int M = ((G >= 8 ? 512 : NZ + 2) + XT - 1) / XT;
+  // exchanged values per hand-off thread: NR*C logits + 2 norms
+  constexpr int M = split_slots<RT, G, XT, MBK, C16>();
   constexpr int HC = G;                             // partners polled per round trip
   // wave partial logits in the MFMA accumulator's own layout, [rt][lg][class][i] = row
   // 16 rt + 4 lg + i: one conflict-free ds_write_b128 per row tile, and the (row, class)
@@ -267,7 +307,10 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
   const int64_t ld = P.ld;
   const int NT = (int)(ld >> 6);
   const int C = P.C, B = P.B, E = P.E;
-  const int NV = NR * C + 2;
+  // exchanged values: the NL logits and, with a prox or ridge term, the two squared norms (nothing
+  // reads them under plain FedAvg: neither published nor waited for)
+  const bool NRM = P.prox || P.reg;
+  const int NL = NR * C, NV = NL + (NRM ? 2 : 0);
   static_assert(NZS % 64 == 0, "the softmax loop must stay wave-uniform");
 
   // block -> (group, slice).  Chained: 8*G blocks are launched and those with
@@ -393,10 +436,19 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
   int pn[RT], lb[RT];
   SpCur lc;
   bool lc_ok = sp_seek(lc, P, grp, ng, T, 0);
+  // (epoch, batch) of a cursor's step st = e * nbat + s, carried as counters beside the cursor: a
+  // division per step and cursor otherwise (about 30 scalar instructions each, one of them right
+  // behind S2); a cursor enters a client at st = 0
+  struct SpES { int e, s; };
+  auto es_next = [](SpES& p, const SpCur& c) {
+    if (c.st == 0) { p.e = 0; p.s = 0; }
+    else if (++p.s == c.nbat) { p.s = 0; ++p.e; }
+  };
+  SpES lces = {0, 0};
   // the step's local row indices (raw) and its client's first row (base): pn = base + raw.
   // (The add is left to the caller, so that issuing the loads does not wait for them.)
   auto fetch_raw = [&](int* raw, int64_t& base) {
-    const int e_ = lc.st / lc.nbat, s_ = lc.st - e_ * lc.nbat;
+    const int e_ = lces.e, s_ = lces.s;
     const int b0_ = s_ * B, bc_ = min(B, lc.n - b0_);
     const int32_t* pp_ = P.perms + (int64_t)E * lc.row0 + (int64_t)e_ * lc.n + b0_;
     base = lc.row0;
@@ -429,7 +481,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
     fetch_rows();
     SP_XLOAD();
     lc_ok = sp_advance(lc, P, grp, ng, T);
-    if (lc_ok) fetch_rows();
+    if (lc_ok) { es_next(lces, lc); fetch_rows(); }
   }
   if constexpr (NCS < NC)                         // the classes the mb softmax never writes
     for (int i = tid; i < NR * NC; i += NTH) gbuf[i / NC][i % NC] = 0.f;
@@ -465,6 +517,11 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
   // client boundaries are branches inside it)
   SpCur cc;
   bool cc_ok = sp_seek(cc, P, grp, ng, T, 0);
+  SpES cces = {0, 0};
+  // 1 / (batch rows) of a full batch and of the client's last one (taken at the client's start),
+  // with the softmax's own expression -- the same bits -- instead of an IEEE division per step
+  const float inv_full = 1.0f / (float)B;
+  float inv_tail = 0.f;
   flush_empty(0, cc_ok ? cc.k : T);
   unsigned gs = 0;                                // steps run by this group in this launch
   bool dead = false;                              // a hand-off timed out: stop waiting
@@ -523,11 +580,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
       }
       if (PROX) anc = (P.chained && cc.j > 0) ? P.W_out + (int64_t)(cc.j - 1) * C * ld : start;
       lsum = 0.0;
+      inv_tail = 1.0f / (float)(n - (nbat - 1) * B);
     }
     {
       SP_STAMP(0)
-      const int e = st / nbat, s = st - e * nbat;
+      const int e = cces.e, s = cces.s;
       const int b0 = s * B, bc = min(B, n - b0);
+      const bool last_e = e == E - 1;               // the only epoch whose loss is kept
       const int par = gs & 1;
       const unsigned tag32 = X.tag_base + gs + 1u;
       if (w == 0 && lg == 0)
@@ -556,7 +615,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) lbn[rt] = P.labels[pn[rt]];
           lcn_ok = sp_advance(lc, P, grp, ng, T);
-          if (lcn_ok) fetch_raw(pnr, pnb);
+          if (lcn_ok) { es_next(lces, lc); fetch_raw(pnr, pnb); }
         }
       };
       if constexpr (TOP_FETCH) fetch_next();
@@ -610,14 +669,18 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
         for (int m = 0; m < M; ++m) {
           const int idx = tid + XT * m;
           float v = 0.f;
-          if (idx < NV - 2) {
+          if (idx < NL) {
             const int r = idx / C, c = idx - r * C;
             const int zo = MB ? zp_off_mb<MB ? MBK : 1>(r, c) : zp_off(r, c);
 #pragma unroll
             for (int i = 0; i < NW; ++i) v += zpart[i][zo];
           } else if (idx < NV) {
+            // (the waves' partials read together, then summed in wave order)
+            float t[NW];
 #pragma unroll
-            for (int i = 0; i < NW; ++i) v += wred[i][idx - (NV - 2)];
+            for (int i = 0; i < NW; ++i) t[i] = wred[i][idx - NL];
+#pragma unroll
+            for (int i = 0; i < NW; ++i) v += t[i];
           }
           own[m] = v;
           sum[m] = 0.f;
@@ -678,11 +741,11 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
         for (int m = 0; m < M; ++m) {
           const int idx = tid + XT * m;
           if (idx < NV) {
-            if (idx < NV - 2) {
+            if (idx < NL) {
               const int r = idx / C, c = idx - r * C;
               zsum[r][c] = sum[m];
             } else {
-              nrm[idx - (NV - 2)] = sum[m];       // ||W - W_a||^2, ||W||^2 at the start of this step
+              nrm[idx - NL] = sum[m];       // ||W - W_a||^2, ||W||^2 at the start of this step
             }
           }
         }
@@ -734,7 +797,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
 #pragma unroll
         for (int f = NE1; f < NE2; ++f) issue_row(f);
       SP_STAMP(6)
-      const float invb = 1.0f / (float)bc;
+      const float invb = s == nbat - 1 ? inv_tail : inv_full;
       float cep = 0.f;
       // (mb: NCS lanes per row, the class blocks' width rounded to a power of 2 -- 4 at C <= 4, 8 at
       // C <= 8; the classes past it stay the zeros written at the kernel's start.  The same sums:
@@ -746,8 +809,12 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
         // (the loop is wave-uniform -- NZS is a multiple of 64 -- so the DPP exchanges run with
         // every lane active)
         float m = valid ? z : -INFINITY;
+        if constexpr (NCS == 16) {
+          m = sp_row16_max(m);
+        } else {
 #pragma unroll
-        for (int off = NCS / 2; off > 0; off >>= 1) m = fmaxf(m, xor_get(m, off, lane));
+          for (int off = NCS / 2; off > 0; off >>= 1) m = fmaxf(m, xor_get(m, off, lane));
+        }
         // softmax on v_exp_f32 / v_rcp_f32 / v_log_f32 (one exponential per entry, e / sum e
         // for the gradient): within the fp32 tolerance of torch's log_softmax (tests/fixtures.py)
         const float ex = valid ? __expf(z - m) : 0.f;
@@ -758,19 +825,23 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
         if (valid) {
           const bool isy = c == lab[par][r];
           gv = (isy ? -invb : 0.f) + ex * __builtin_amdgcn_rcpf(se) * invb;
-          if (isy) cep -= z - m - __logf(se);
         }
         gbuf[r][c] = gv;
+        // the cross-entropy only where its loss is kept (wave-uniform: the earlier epochs skip the
+        // logarithm here and the wave sum below)
+        if (last_e && valid && c == lab[par][r]) cep -= z - m - __logf(se);
       }
-      cep = wave_sum_dpp(cep, lane);
-      if (lane == 0) wce[w] = cep;
+      if (last_e) {
+        cep = wave_sum_dpp(cep, lane);
+        if (lane == 0) wce[w] = cep;
+      }
       team_sync();  // S3: g, CE partials
       if constexpr (NE > 0)
 #pragma unroll
         for (int f = NE2; f < NE; ++f) issue_row(f);
       SP_STAMP(7)
-      const float pn2 = nrm[0], wn2 = nrm[1];
-      if (g == 0 && tid == 0 && e == E - 1) {
+      const float pn2 = NRM ? nrm[0] : 0.f, wn2 = NRM ? nrm[1] : 0.f;
+      if (g == 0 && tid == 0 && last_e) {
         float ce = 0.f;
         for (int i = 0; i < NW; ++i) ce += wce[i];
         float loss = ce / (float)bc;
@@ -1059,6 +1130,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
     }
     const int kprev = cc.k;
     cc_ok = sp_advance(cc, P, grp, ng, T);
+    if (cc_ok) es_next(cces, cc);
     flush_empty(kprev + 1, cc_ok ? cc.k : T);
   }
 #undef SP_XLOAD
@@ -1075,6 +1147,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void local_train_split_kernel(LTPara
 #ifndef FS_SPLIT_KERNEL_ONLY   // (scripts/split_asm.sh: one instance's code, without the instance selection)
 template <int RT, int G, bool PROX, int EARLY, int TEAMS, int WAVES = SP_WAVES, int TPWK = SP_TPW, int MBK = 0>
 static void launch_split_k(const LTParams& P, const SplitWS& X, int grid, size_t lds, hipStream_t st) {
+  constexpr int XT = WAVES / TEAMS * 64;
+  if constexpr (MBK < SP_MBK_C16 && split_slots<RT, G, XT, MBK, true>() != split_slots<RT, G, XT, MBK, false>()) {
+    if (P.C > SP_C1) {                             // C = 16: the two-slot instance
+      launch_split_k<RT, G, PROX, EARLY, TEAMS, WAVES, TPWK, MBK | SP_MBK_C16>(P, X, grid, lds, st);
+      return;
+    }
+  }
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(
         reinterpret_cast<const void*>(&local_train_split_kernel<RT, G, PROX, EARLY, TEAMS, WAVES, TPWK, MBK>),

@@ -1,6 +1,6 @@
 """Diagnostic: fs_local_train launch time at a BASELINE config shape under fs_tuning overrides.
 
-    python scripts/lt_tuning_sweep.py --config 2 --field split_poll_delay --values -1,2,4,8   (GPU box)
+    python scripts/lt_tuning_sweep.py --config 2 --field split_poll_delay --values=-1,2,4,8 [--G 4] [--prox]   (GPU box)
 
 Event-timed mean of --reps launches of the planner's form after 3 warm-up launches, one line per value."""
 import argparse
@@ -23,6 +23,8 @@ def main():
     ap.add_argument('--field', default='split_poll_delay')
     ap.add_argument('--values', default='-1,2,4,8')
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--G', type=int, default=0, help='group width (0: the planner\'s choice)')
+    ap.add_argument('--prox', action='store_true', help="FedProx's prox term (mu = 1e-3)")
     a = ap.parse_args()
     sh = SHAPES[a.config]
     dev = torch.device('cuda')
@@ -31,7 +33,7 @@ def main():
     feats = engine.Features(d['X_train'], d['y_train'], D, dev)
     del d
     ch = sh.get('chained', False)
-    tr = engine.LocalTrainer(feats, C, B, E, chained=ch)
+    tr = engine.LocalTrainer(feats, C, B, E, split=(a.G or None), chained=ch, prox=a.prox)
     torch.manual_seed(0)
     tr.upload_perms(rng.draw_pass_seeds(N * E))
     W0 = torch.zeros(C, feats.ld, device=dev)
@@ -40,12 +42,12 @@ def main():
     for v in [int(x) for x in a.values.split(',')]:
         with L.tuning(**{a.field: v}):
             for _ in range(3):
-                tr.run(W0, 0.5, False, 0.0, False, 0.0, ch)
+                tr.run(W0, 0.5, a.prox, 1e-3, False, 0.0, ch)
             ts = []
             for _ in range(a.reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                tr.run(W0, 0.5, False, 0.0, False, 0.0, ch)
+                tr.run(W0, 0.5, a.prox, 1e-3, False, 0.0, ch)
                 e1.record()
                 ts.append((e0, e1))
             torch.cuda.synchronize()
