@@ -348,6 +348,53 @@ int fs_aggregate_nova(const float* d_W_all, int64_t stride, const int32_t* d_sel
                       float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * SCAFFOLD (Karimireddy et al., ICML 2020; option II).  Additive to ABI 23: three new entry
+ * points, no new field in fs_tuning or fs_plan_desc, FS_ABI_VERSION unchanged.
+ *
+ * fs_local_train_scaffold: local training with control variates, parallel clients,
+ * cross-entropy.  One 512-thread workgroup per client of d_order (NULL: clients 0..N-1); grid N.
+ * Under a subset launch N is the sample size and d_order holds the ids; d_W_out [clients][C][ld],
+ * d_ci [clients][C][ld] and d_loss [clients] stay indexed by client id and entries of clients
+ * outside d_order are not touched.  Client i starts from y = d_W_start and takes fs_local_train's
+ * K_i = E*ceil(n_i/B) steps (single form: same tiling, sums and ownership) with one more gradient
+ * term: d = fl(c - c_i), fixed for the whole client, grad = fl(grad_CE + d), then the ridge term
+ * (reg), then y -= lr*grad.  The reported loss is fs_local_train's (the correction is no part of
+ * it).  After the last step, in place:
+ *     c_i <- fl(fl(c_i - c) + fl(fl(x - y) * inv)),   inv = 1.0f / fl((float)K_i * lr)
+ * with x = d_W_start, every operation rounded separately, and d_W_out[i] = y.  With c = c_i = 0
+ * d_W_out and d_loss are bitwise fs_local_train's at G = 1.  A client without steps (E = 0)
+ * returns x, loss 0 and an unchanged c_i.  d_c [C][ld] is only read; d_W_start must not alias
+ * d_W_out.  There is no prox term and no chained, wide, split or MSE form.
+ * Requirements: 1 <= C <= 32, 1 <= B, ld % 64 == 0, lr > 0, non-null pointers (d_order may be
+ * NULL): FS_EINVAL otherwise, and FS_EUNSUPPORTED for B > 64 -- before any launch, outputs
+ * untouched.
+ *
+ * fs_aggregate_scaffold: the server step, both folds from one pass over the M rows d_sel (NULL:
+ * rows 0..M-1) of d_W_all, in place, with x = d_W_g on entry:
+ *     d_W_g <- fl(x + sum_k fl(q_k * fl(W_k - x)))
+ *     d_c   <- fl(fl(cs * c) + sum_k fl(r_k * fl(x - W_k)))
+ * k ascending, every operation rounded separately.  With q_k = eta_g p_k / sum_S p,
+ * r_k = p_k / (K_k lr) and cs = 1 - sum_S p_k (0 when S is every client) d_c stays
+ * sum_j p_j c_j over ALL clients to rounding, since option II's c_i+ - c_i = -c + (x - W_i)/(K_i lr)
+ * does not need the old c_i.  Regimes are fs_aggregate's, chosen by M and chunks: the exact left
+ * fold for M < 16 or chunks == 1, else the same sub-ranges, chunks and stage-2 tree; the two-stage
+ * form keeps two partials per chunk in d_ws, so its chunk clamp uses ws_floats / 2.  d_W_g is
+ * bitwise what fs_aggregate_nova returns in mode FS_NOVA_UPDATES with base d_W_g, the same q and
+ * chunks and a workspace of ws_floats / 2; d_c has the same fold structure over its own terms
+ * (the first term of a range is the term itself, fl(cs * c) is added last).  A position's x and c
+ * are read by the workgroup that writes them, before it writes.  (M + 2)*len floats read, 2*len
+ * written.  FS_EINVAL for M < 1, len or stride no multiple of 4, a null pointer (d_sel and d_ws
+ * may be NULL) or d_W_g == d_c; nothing is written then.
+ * ------------------------------------------------------------------------- */
+int fs_local_train_scaffold(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
+                            const int32_t* d_perms, const int32_t* d_order, int N, int C, int B, int E,
+                            float lr, float lam, int reg, const float* d_W_start, const float* d_c,
+                            float* d_ci, float* d_W_out, double* d_loss, void* stream);
+int fs_aggregate_scaffold(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q,
+                          const float* d_r, float cs, int M, int64_t len, float* d_W_g, float* d_c,
+                          float* d_ws, int64_t ws_floats, int chunks, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation.  Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -740,6 +787,21 @@ int fs_plan_round_subset(fs_plan* plan, int t, float lr, int phases, const int32
  * else about the plan changes.  FS_EINVAL for mode 2 on a chained plan (a chained client's
  * W_j - W_g contains its predecessors' work), mode 1 with a null d_b, or another mode. */
 int fs_plan_set_nova(fs_plan* plan, int mode, const float* d_b, float te, float s0);
+
+/* (additive to ABI 23) SCAFFOLD rounds.  Host state read when the next round call enqueues, as
+ * fs_plan_set_nova's.  on = 1: TRAIN launches fs_local_train_scaffold (the plan's G and workspace
+ * are ignored) with d_c [C][ld] and d_ci [N][C][ld]; AGGREGATE launches fs_aggregate_scaffold with
+ * the round's d_q (d_p, the override, or the subset call's d_q), d_r ([N]; [M] of a subset round)
+ * and cs, updating d_W_g and d_c in place.  d_r and cs change with the round's lr and sample: call
+ * again before each round, which is allowed whatever the plan holds while it is on.  Subset
+ * rounds, chunked shuffles and the device replay work unchanged.  A deferred evaluation is never
+ * fused while it is on: it runs as an fs_eval launch of its own before the next TRAIN, as on
+ * loss = 1 plans.  d_c, d_ci and d_r are read (d_c, d_ci also written) asynchronously by the
+ * launches: keep them alive.  on = 0 restores the plan as it was (the pointers are ignored).
+ * FS_EINVAL for a chained plan, loss = 1, B > 64, a plan with prox on, a nova mode other than 0,
+ * a null pointer with on = 1, or turning it on while the plan holds a pending evaluation
+ * (fs_plan_eval_flush first). */
+int fs_plan_set_scaffold(fs_plan* plan, int on, float* d_c, float* d_ci, const float* d_r, float cs);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

@@ -43,6 +43,13 @@ _SIGS = {
     'fs_aggregate_nova': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                     C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_int, C.c_void_p]),
+    # SCAFFOLD (additive to ABI 23)
+    'fs_local_train_scaffold': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fs_aggregate_scaffold': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'fs_plan_set_scaffold': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -331,6 +338,9 @@ KERNEL_SOURCES = {
     'mix_solve_mse': ('mixture_mse.hip', 'mse_rows.h', 'common.h'),
     'z_eval': ('z_eval.hip', 'common.h'),
     'aggregate_nova': ('aggregate_nova.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
+    'local_train_scaffold': ('local_train_scaffold.hip', 'scaffold.h', 'common.h'),
+    'aggregate_scaffold': ('aggregate_scaffold.hip', 'aggregate.hip', 'aggregate_sel.h', 'scaffold.h', 'finalize.h',
+                           'common.h'),
 }
 
 

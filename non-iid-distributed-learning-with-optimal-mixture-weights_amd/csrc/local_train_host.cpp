@@ -9,6 +9,7 @@
 #include <unordered_map>
 
 #include "local_train_wide.h"
+#include "scaffold.h"
 #include "split_common.h"
 
 namespace fs {
@@ -326,9 +327,41 @@ int local_train(const float* d_phi, int64_t ld, const int64_t* d_row_off, const 
   return FS_OK;
 }
 
+// ---- SCAFFOLD (local_train_scaffold.hip): the single form with control variates -------------------
+// One workgroup per client of d_order, no workspace and no planner: parallel clients,
+// cross-entropy, B <= 64, no prox term.  Nothing is launched or written on a violation.
+int local_train_scaffold(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
+                         const int32_t* d_perms, const int32_t* d_order, int N, int C, int B, int E, float lr,
+                         float lam, int reg, const float* d_W_start, const float* d_c, float* d_ci, float* d_W_out,
+                         double* d_loss, hipStream_t st) {
+  FS_REQUIRE(N >= 1, "N must be >= 1");
+  FS_REQUIRE(C >= 1 && C <= 32, "num_classes must be in [1, 32]");
+  FS_REQUIRE(B >= 1, "batch_size must be >= 1");
+  if (B > 64)
+    return fail(FS_EUNSUPPORTED, "fs_local_train_scaffold: batch_size above 64 is not provided (no wide form with variates)");
+  FS_REQUIRE(E >= 0, "epoch must be >= 0");
+  FS_REQUIRE(ld >= 64 && ld % 64 == 0, "ld must be a positive multiple of 64");
+  FS_REQUIRE(lr > 0.f, "lr must be > 0 (the new variate divides by K * lr)");
+  FS_REQUIRE(d_phi && d_row_off && d_labels && d_perms && d_W_start && d_c && d_ci && d_W_out && d_loss, "null pointer");
+  const LTSParams P{d_phi, ld, d_row_off, d_labels, d_perms, d_order, N, C, B, E, lr, lam, reg ? 1 : 0,
+                    d_W_start, d_c, d_ci, d_W_out, d_loss};
+  const int rc = launch_local_train_scaffold(P, st);
+  if (rc != FS_OK) return rc;
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
 }  // namespace fs
 
 using namespace fs;
+
+extern "C" int fs_local_train_scaffold(const float* d_phi, int64_t ld, const int64_t* d_row_off, const int32_t* d_labels,
+                                       const int32_t* d_perms, const int32_t* d_order, int N, int C, int B, int E,
+                                       float lr, float lam, int reg, const float* d_W_start, const float* d_c,
+                                       float* d_ci, float* d_W_out, double* d_loss, void* stream) {
+  return fs::local_train_scaffold(d_phi, ld, d_row_off, d_labels, d_perms, d_order, N, C, B, E, lr, lam, reg, d_W_start,
+                                  d_c, d_ci, d_W_out, d_loss, reinterpret_cast<hipStream_t>(stream));
+}
 
 extern "C" int fs_local_train_last_kernel(void) { return t_last_lt; }
 

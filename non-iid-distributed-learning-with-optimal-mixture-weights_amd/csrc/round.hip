@@ -28,6 +28,11 @@
 //
 // FedNova (ABI 23, fs_plan_set_nova): AGGREGATE of either kind of round launches fs_aggregate_nova
 // (aggregate_nova.hip) instead, with the round's weights as q and d_W_g as the base it updates.
+//
+// SCAFFOLD (additive to ABI 23, fs_plan_set_scaffold): TRAIN launches fs_local_train_scaffold
+// (local_train_scaffold.hip; the plan's G and workspace are ignored) and AGGREGATE launches
+// fs_aggregate_scaffold (aggregate_scaffold.hip), which updates d_W_g and the server variate from one
+// pass over the round's rows.  A deferred evaluation is never fused while it is on.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,6 +54,7 @@
 #include "mse_rows.h"
 #include "mt_replay.h"
 #include "randperm_geom.h"
+#include "scaffold.h"
 
 // RP_CAPPED = 0 (build macro, A/B): the plan's replays keep the uncapped geometry everywhere
 #ifndef RP_CAPPED
@@ -164,6 +170,12 @@ struct fs_plan {
   int nova_mode = 0;
   const float* nova_b = nullptr;
   float nova_te = 1.f, nova_s0 = 1.f;
+  // fs_plan_set_scaffold: TRAIN is fs_local_train_scaffold and AGGREGATE fs_aggregate_scaffold while on
+  int scaffold = 0;
+  float* sc_c = nullptr;              // [C][ld] server variate
+  float* sc_ci = nullptr;             // [N][C][ld] client variates
+  const float* sc_r = nullptr;        // [N], or [M] of a subset round
+  float sc_cs = 0.f;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -687,6 +699,9 @@ static int plan_train(fs_plan* p, const int32_t* perms, int t, float lr, const f
   double* loss = d.d_loss_hist + (int64_t)t * d.N;
   const int n = sub ? sub->M : d.N;
   const int32_t* order = sub ? sub->order : d.d_order;
+  if (p->scaffold)
+    return fs::local_train_scaffold(d.d_phi, d.ld, d.d_row_off, d.d_labels, perms, order, n, d.C, d.B, d.E, lr, d.lam,
+                                    d.reg, d.d_W_g, p->sc_c, p->sc_ci, d.d_W_out, loss, st);
   if (d.loss)
     return fs::local_train_mse(d.d_phi, d.ld, d.d_row_off, d.d_y, perms, order, n, d.B, d.E, lr, d.mu, d.prox,
                                d.lam, d.reg, d.chained, d.d_W_g, d.d_W_out, loss, st);
@@ -736,7 +751,8 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
     const int rc = fs::eval_finalize_launch(f.part, f.nb, f.n, f.out, st);
     if (rc != FS_OK) return rc;
   }
-  const bool fused = (phases & FS_PHASE_TRAIN) && p->eval_pending >= 0 && p->fuse_E > 0;
+  // (SCAFFOLD's training launch is one workgroup per client and carries no evaluation: never fused)
+  const bool fused = (phases & FS_PHASE_TRAIN) && p->eval_pending >= 0 && p->fuse_E > 0 && !p->scaffold;
   if (p->eval_pending >= 0 && !fused) {
     const int rc = flush_eval(p, st);
     if (rc != FS_OK) return rc;
@@ -799,7 +815,14 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
     const int M = sub ? sub->M : d.N;
     const fs::EvalFinalize* f = with_fin ? &fin : nullptr;
     int rc;
-    if (p->nova_mode)
+    if (p->scaffold) {
+      // (no finaliser rides on the dual fold: none is pending while SCAFFOLD is on, but one left
+      // by a call before the setter would be lost -- it runs as a launch of its own)
+      rc = with_fin ? fs::eval_finalize_launch(fin.part, fin.nb, fin.n, fin.out, st) : FS_OK;
+      if (rc == FS_OK)
+        rc = fs::aggregate_scaffold_launch(d.d_W_out, len, sel, pw, p->sc_r, p->sc_cs, M, len, d.d_W_g, p->sc_c,
+                                           d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, st);
+    } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
     else if (sub)
@@ -837,6 +860,38 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
   p->nova_s0 = s0;
+  return FS_OK;
+}
+
+// Additive to ABI 23: SCAFFOLD rounds from now on (host state, read when a round call enqueues, as
+// fs_plan_set_nova's).  on = 1: TRAIN launches fs_local_train_scaffold with the server variate d_c
+// [C][ld] and the client variates d_ci [N][C][ld], AGGREGATE launches fs_aggregate_scaffold with the
+// round's weights as q, d_r ([N]; [M] of a subset round) and cs, updating d_W_g and d_c in place.
+// d_r and cs change with the round's lr and sample: call again before each round (allowed while
+// on, whatever the plan holds).  Turning it on is refused while the plan holds a pending
+// evaluation (fs_plan_eval_flush first).  on = 0: the plan as it was.
+extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci, const float* d_r, float cs) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->scaffold = 0;
+    p->sc_c = p->sc_ci = nullptr;
+    p->sc_r = nullptr;
+    p->sc_cs = 0.f;
+    return FS_OK;
+  }
+  FS_REQUIRE(d_c && d_ci && d_r, "null pointer");
+  FS_REQUIRE(!p->d.chained, "SCAFFOLD needs parallel clients");
+  FS_REQUIRE(p->d.loss == 0, "SCAFFOLD is implemented for cross-entropy only");
+  FS_REQUIRE(p->d.B <= 64, "SCAFFOLD needs batch_size <= 64");
+  FS_REQUIRE(!p->d.prox, "the prox term is not supported together with SCAFFOLD");
+  FS_REQUIRE(p->nova_mode == 0, "SCAFFOLD and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
+             "the plan holds a pending evaluation (fs_plan_eval_flush first)");
+  p->scaffold = 1;
+  p->sc_c = d_c;
+  p->sc_ci = d_ci;
+  p->sc_r = d_r;
+  p->sc_cs = cs;
   return FS_OK;
 }
 

@@ -302,6 +302,35 @@ class LocalTrainer:
         self.shuffler.release(slot)
         return self.W_out, loss
 
+    def run_scaffold(self, W_start, lr, reg, lam, c, ci, slot=0, loss_out=None, sel=None):
+        """fs_local_train_scaffold: SCAFFOLD's local training of every client (``sel``: of the
+        sampled clients, as ``run``) from ``W_start`` with the server variate ``c`` [C, ld] and the
+        client variates ``ci`` [N, C, ld], float32 device tensors; ``ci`` rows of the trained clients
+        are replaced by their new variates (option II), in place.  Parallel clients, cross-entropy,
+        one workgroup per client whatever ``split`` the trainer was planned with; no prox term."""
+        if self.task != 'ce' or self.chained:
+            raise ValueError('run_scaffold needs a cross-entropy trainer with parallel clients')
+        f = self.f
+
+        def f32(x, n):
+            return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n
+        if not (f32(c, self.C * f.ld) and f32(ci, self.N * self.C * f.ld)):
+            raise ValueError('run_scaffold: c [C, ld] and ci [N, C, ld] must be contiguous float32 device tensors')
+        loss = self.loss if loss_out is None else loss_out
+        n_run, order = self.N, self.order
+        if sel is not None:
+            order = torch.from_numpy(self.sel_order(sel)).to(f.device)
+            n_run = int(order.numel())
+        perms = self.shuffler.acquire(slot)
+        _lib.check(_lib.lib().fs_local_train_scaffold(_lib.ptr(f.phi), f.ld, _lib.ptr(f.row_off_dev),
+                                                      _lib.ptr(f.labels), _lib.ptr(perms), _lib.ptr(order), n_run,
+                                                      self.C, self.B, self.E, float(lr), float(lam), int(bool(reg)),
+                                                      _lib.ptr(W_start), _lib.ptr(c), _lib.ptr(ci),
+                                                      _lib.ptr(self.W_out), _lib.ptr(loss), _lib.stream_ptr()),
+                   'fs_local_train_scaffold')
+        self.shuffler.release(slot)
+        return self.W_out, loss
+
 
 class RoundPlan:
     """fs_plan: the native round driver (csrc/round.hip).  One ``round`` call enqueues a
@@ -409,6 +438,24 @@ class RoundPlan:
                                                float(s0)), 'fs_plan_set_nova')
         self._nova_b = b
 
+    def set_scaffold(self, on, c=None, ci=None, r=None, cs=0.0):
+        """fs_plan_set_scaffold: SCAFFOLD rounds from now on -- TRAIN launches
+        fs_local_train_scaffold with the server variate ``c`` [C, ld] and the client variates ``ci``
+        [N, C, ld], AGGREGATE fs_aggregate_scaffold with the round's weights as ``q``, ``r`` ([N]; [M]
+        of a subset round) and ``cs``, updating ``W_g`` and ``c`` in place.  Float32 device tensors the
+        launches read asynchronously (the plan keeps the last ones alive).  ``r`` and ``cs`` change
+        with the round's lr and sample: call again before each round.  ``on`` false restores the plan."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_scaffold(self._h, 0, None, None, None, 0.0), 'fs_plan_set_scaffold')
+            self._scaffold = None
+            return
+        for x in (c, ci, r):
+            if x is not None and not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+                raise ValueError('set_scaffold: c, ci and r must be contiguous float32 device tensors')
+        _lib.check(_lib.lib().fs_plan_set_scaffold(self._h, 1, _lib.ptr(c), _lib.ptr(ci), _lib.ptr(r), float(cs)),
+                   'fs_plan_set_scaffold')
+        self._scaffold = (c, ci, r)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -494,6 +541,36 @@ class Aggregator:
                                                 _lib.ptr(out), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
                                                 _lib.stream_ptr()), 'fs_aggregate_nova')
         return out
+
+    def run_scaffold(self, W_all, q, r, cs, W_g, c, sel=None, check=True):
+        """fs_aggregate_scaffold: SCAFFOLD's server step from one pass over the rows ``sel`` of
+        ``W_all`` (None: rows 0..len(q)-1), both in place with x = ``W_g`` on entry:
+        ``W_g = x + sum_k q_k*(W_k - x)`` -- bitwise ``run_nova`` mode 2 on a workspace of half the
+        size -- and ``c = cs*c + sum_k r_k*(x - W_k)``, in the regimes of ``run`` at len(q) clients.
+        ``check`` as in ``run_sel``."""
+        M = int(q.numel())
+
+        def f32(x):
+            return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if not (f32(q) and f32(r) and M >= 1 and r.numel() == M and f32(W_g) and f32(c)
+                and W_g.numel() >= self.len and c.numel() >= self.len):
+            raise ValueError('run_scaffold: q, r (float32, equal non-zero length), W_g and c (float32, len) must be '
+                             'contiguous device tensors')
+        if sel is not None:
+            if not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == M):
+                raise ValueError('run_scaffold: sel must be a contiguous int32 device tensor as long as q')
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('run_scaffold: q is longer than W_all has rows')
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_scaffold: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_scaffold(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                                    _lib.ptr(q), _lib.ptr(r), float(cs), M, self.len, _lib.ptr(W_g),
+                                                    _lib.ptr(c), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
+                                                    _lib.stream_ptr()), 'fs_aggregate_scaffold')
+        return W_g, c
 
 
 class Evaluator:

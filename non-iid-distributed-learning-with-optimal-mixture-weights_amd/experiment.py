@@ -53,7 +53,8 @@ from . import engine
 NAMES = ['CL', 'DL', 'FedAMW_OneShot', 'FedAvg', 'FedProx', 'FedAMW']
 # exp.py:124 leaves its FedNova call commented out: it runs only when ``algos`` names it, and its
 # rows are then appended after the six above (the default result layout is unchanged)
-EXTRA = ['FedNova']
+# Scaffold (not in the reference) likewise: its row comes after FedNova's
+EXTRA = ['FedNova', 'Scaffold']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -203,6 +204,18 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
                                                        Round, stats=st, **fpar))
             keep_participants('FedNova', st)
             train_mat[6, :, t], error_mat[6, :, t], acc_mat[6, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        if 'Scaffold' in algos:
+            # FedAvg's arguments; clients are always parallel (classification only)
+            st = ce('Scaffold', False)
+            if participation is not None:
+                st = st or {}
+            spar = dict(kw) if participation is None else dict(participation=participation, sample_seed=sample_seed,
+                                                               **kw)
+            r = timed('Scaffold', lambda: tools.Scaffold(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False,
+                                                         0, Round, stats=st, **spar))
+            keep_participants('Scaffold', st)
+            k = names.index('Scaffold')
+            train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -235,7 +248,8 @@ def main(argv=None):
     ap.add_argument('--result-dir', default='./results')
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES),
-                    help='comma-separated; FedNova (exp.py:124, commented out there) runs only when named here')
+                    help='comma-separated; FedNova (exp.py:124, commented out there) and Scaffold run only when named '
+                         'here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -243,7 +257,7 @@ def main(argv=None):
                     help="score the round's global model / every client's own model on each client's own rows")
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
-                         'Applies to the FedAvg, FedProx and FedNova calls only, which then run with parallel clients '
+                         'Applies to the FedAvg, FedProx, FedNova and Scaffold calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')

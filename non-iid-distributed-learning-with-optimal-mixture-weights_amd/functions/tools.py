@@ -1,4 +1,4 @@
-"""Drop-in FedAvg / FedProx / FedNova / FedAMW on MI355X.
+"""Drop-in FedAvg / FedProx / FedNova / FedAMW (and SCAFFOLD) on MI355X.
 
 Same names, positional signatures, defaults and return values as the reference
 (/root/reference/functions/tools.py:329, 356, 383, 413):
@@ -50,7 +50,7 @@ Keyword-only extensions (not in the reference):
   clients into one and raises a ValueError.  Nothing is drawn from any generator and the
   returns are bitwise those of the run without the key.
 
-* ``participation`` / ``sample_seed`` (FedAvg, FedProx, FedNova; needs ``clients='parallel'``) -- partial
+* ``participation`` / ``sample_seed`` (FedAvg, FedProx, FedNova, Scaffold; needs ``clients='parallel'``) -- partial
   client participation: only a sampled subset S_t of the clients trains in round t and is
   aggregated, ``W_g = sum_{j in S_t} q_j W_j`` with ``q = n[S_t] / sum(n[S_t])`` folded in ascending
   client id (fs_aggregate_sel reads the sampled rows only).  A float in (0, 1] is McMahan's
@@ -67,6 +67,10 @@ Keyword-only extensions (not in the reference):
 * ``variant`` (FedNova) -- ``'reference'`` (default): the reference's aggregate, tools.py:401-405,
   bitwise its fold (fs_aggregate_nova mode 1); ``'updates'``: Wang et al.'s normalised averaging
   of the clients' updates (mode 2; needs ``clients='parallel'``).  See ``FedNova`` and DESIGN 4.2.2.
+
+* ``Scaffold`` (not in the reference) -- SCAFFOLD with control variates, FedAvg's positional list,
+  parallel clients; keyword-only ``server_lr``, ``weighting``, ``participation`` / ``sample_seed``
+  (see ``Scaffold`` and DESIGN 4.1 / 4.2.3).
 
 All arithmetic of the round runs in the gfx950 kernels of libfedsim.so; there is no
 CPU path.
@@ -90,7 +94,7 @@ from .. import _lib
 from . import participation as _participation
 from .._lib import FedsimError
 
-__all__ = ['FedAvg', 'FedProx', 'FedAMW', 'Centralized', 'Distributed', 'FedAMW_OneShot', 'Federation', 'RFF',
+__all__ = ['FedAvg', 'FedProx', 'FedNova', 'Scaffold', 'FedAMW', 'Centralized', 'Distributed', 'FedAMW_OneShot', 'Federation', 'RFF',
            'feature_mapping', 'update_learning_rate', 'init_weights']
 
 
@@ -303,15 +307,73 @@ def nova_update_coefficients(ns, epoch, batch_size):
     return p, (p.to(torch.float64) * tau_eff / tau).to(torch.float32)
 
 
+SCAFFOLD_WEIGHTINGS = ('size', 'uniform')
+
+
+def _check_scaffold(type, prox, batch_size, weighting, server_lr):
+    """Scaffold's keyword checks (host only: before any device is touched)."""
+    if type != 'classification':
+        raise ValueError("Scaffold is implemented for type='classification' (cross-entropy) only")
+    if prox:
+        raise ValueError('the prox term is not supported together with SCAFFOLD (prox=False)')
+    if int(batch_size) > 64:
+        raise ValueError('Scaffold needs batch_size <= 64 (the variate kernel has no batch-tiled form)')
+    if weighting not in SCAFFOLD_WEIGHTINGS:
+        raise ValueError("weighting must be 'size' or 'uniform'")
+    if not float(server_lr) > 0.0:
+        raise ValueError('server_lr must be > 0')
+
+
+def scaffold_lr_schedule(lr, R):
+    """The learning rate of every round: ``update_learning_rate`` compounded as the round loop
+    rebinds it (lr0, lr0/10, lr0/1000)."""
+    out = []
+    for t in range(int(R)):
+        lr = update_learning_rate(t, lr, R)
+        out.append(lr)
+    return out
+
+
+def scaffold_weights(ns, weighting='size'):
+    """The clients' global weights p (float64): n_i / n ('size') or 1 / N ('uniform')."""
+    ns = np.asarray(ns, dtype=np.float64)
+    if weighting == 'uniform':
+        return np.full(len(ns), 1.0 / len(ns))
+    return ns / float(np.sum(ns))
+
+
+def scaffold_round_coefficients(ns, S, epoch, batch_size, lr, server_lr=1.0, weighting='size'):
+    """SCAFFOLD's host scalars of one round with the sample ``S`` (ascending ids) at the round's
+    learning rate ``lr``, in float64, each rounded once to float32:
+    q_k = server_lr * p_k / sum_S p (the model fold), r_k = p_k / (K_k * lr) with
+    K_k = E * ceil(n_k / B) (the variate fold), cs = 1 - sum_S p_k -- exactly 0 when S is every
+    client -- and w_k = p_k / sum_S p (train_loss).  Returns (q, r, cs, w): float32 arrays and a float."""
+    ns = np.asarray(ns, dtype=np.int64)
+    S = np.asarray(S, dtype=np.int64)
+    p = scaffold_weights(ns, weighting)[S]
+    psum = float(np.sum(p))
+    K = (int(epoch) * -(-ns[S] // int(batch_size))).astype(np.float64)
+    q = (float(server_lr) * p / psum).astype(np.float32)
+    r = (p / (K * float(lr))).astype(np.float32)
+    cs = 0.0 if len(S) == len(ns) else float(np.float32(1.0 - psum))
+    return q, r, cs, (p / psum).astype(np.float32)
+
+
 class Federation:
     """One algorithm call split into setup / rounds / results (bench.py drives the
     rounds one at a time through the same code path as the drop-ins)."""
 
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
-                 shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference'):
+                 shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
+                 server_lr=1.0, weighting='size'):
         if algo == 'fednova':
             _check_nova(variant, clients)
+        self.scaffold = algo == 'scaffold'
+        if self.scaffold:
+            if clients != 'parallel':
+                raise ValueError("Scaffold needs clients='parallel': every client starts from the round's global model")
+            _check_scaffold(type, prox, batch_size, weighting, server_lr)
         opts = dict(OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -334,8 +396,8 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova'):
-                raise NotImplementedError('participation is implemented for FedAvg, FedProx and FedNova only')
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold'):
+                raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova and Scaffold only')
             if self.chained:
                 raise ValueError("participation needs clients='parallel': every sampled client starts from the "
                                  "round's global model (clients='sequential' chains all clients)")
@@ -344,6 +406,8 @@ class Federation:
             self.sched = _participation.make_schedule(len(y_train), int(round), participation, sample_seed)
         if algo == 'fednova' and nranks > 1:
             raise NotImplementedError('FedNova over more than one torch.distributed rank is not implemented')
+        if self.scaffold and nranks > 1:
+            raise NotImplementedError('Scaffold over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -455,8 +519,32 @@ class Federation:
                         q_h[t, :len(S)] = nova_update_coefficients(ns[S], E, B)[1]
                         self.nova_round.append((1.0, 1.0))
                 self.nova_b_dev = b_h.to(dev)
+            if self.scaffold:
+                q_h.zero_()          # SCAFFOLD's own q (below), not n[S] / sum(n[S])
             self.sel_dev = torch.from_numpy(sel_h).to(dev)
             self.sel_order_dev = torch.from_numpy(ord_h).to(dev)
+        if self.scaffold:
+            # SCAFFOLD: the variates (all zero before round 0) and the q / r / cs tables of every
+            # round, built on the host once and uploaded before round 0 (r and cs change with the
+            # round's lr and sample; the launches read them asynchronously)
+            self.c_var = torch.zeros(C, ld, device=dev, dtype=torch.float32)
+            self.ci_var = torch.zeros(N, C, ld, device=dev, dtype=torch.float32)
+            lrs = scaffold_lr_schedule(lr, R)
+            Mx = N if self.sched is None else q_h.shape[1]
+            if self.sched is None:
+                q_h = torch.zeros(R, Mx, dtype=torch.float32)
+            r_h = torch.zeros(R, Mx, dtype=torch.float32)
+            self.sc_cs, self.sc_w = [], []
+            for t in range(R):
+                S = np.arange(N) if self.sched is None else self.sched[t]
+                q, r, cs, w = scaffold_round_coefficients(ns, S, E, B, lrs[t], server_lr, weighting)
+                q_h[t, :len(S)], r_h[t, :len(S)] = torch.from_numpy(q), torch.from_numpy(r)
+                self.sc_cs.append(cs)
+                self.sc_w.append(torch.from_numpy(w))
+            self.sc_r_dev = r_h.to(dev)
+            self.sc_q_dev = q_h.to(dev)
+            self.c_hist = torch.empty(R, C, ld, device=dev) if (stats is not None and stats.get('trace')) else None
+        if self.sched is not None:
             self.q_dev = q_h.to(dev)
         self.eval_hist = torch.empty(R, 2, dtype=torch.float64, device=dev)
         self.W_hist = torch.empty(R, C, ld, device=dev) if (stats is not None and stats.get('trace')) else None
@@ -558,6 +646,8 @@ class Federation:
             ev.append((name, a, b))
             return out
 
+        if self.scaffold:
+            self.plan.set_scaffold(True, self.c_var, self.ci_var, self.sc_r_dev[t], self.sc_cs[t])
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -569,7 +659,7 @@ class Federation:
                 self.plan.round_subset(t, self.lr, phases, self.sel_dev[t], self.sel_order_dev[t], self.q_dev[t], M)
         else:
             def plan_round(phases):
-                self.plan.round(t, self.lr, phases)
+                self.plan.round(t, self.lr, phases, self.sc_q_dev[t] if self.scaffold else None)
         timed('train', lambda: plan_round(P[0]))
         # (under participation the two evaluations of the clients' OWN models below still score all
         # N rows of W_out -- stale rows of clients that sat the round out, zeros before a client's
@@ -637,6 +727,8 @@ class Federation:
             timed('local_eval_global', lambda: self.local_eval.run(self.W_g, 0, self.local_hist['global'][t]))
         if self.W_hist is not None:
             self.W_hist[t].copy_(self.W_g)
+        if self.scaffold and self.c_hist is not None:
+            self.c_hist[t].copy_(self.c_var)
         self.t += 1
         if self.chunk > 1:
             if t % self.chunk == 0 and t >= self.chunk:      # chunk c started: prepare chunk c + 1
@@ -674,7 +766,10 @@ class Federation:
         train_loss, test_loss, test_acc = torch.zeros(self.R), torch.zeros(self.R), torch.zeros(self.R)
         for t in range(R):
             pt = ph[t] if ph is not None else self.p_all
-            if self.sched is not None:     # the sampled clients' weights and losses, ascending client id
+            if self.scaffold:              # sum_S (q_k / server_lr) * loss_k, ascending client id
+                S = np.arange(self.N) if self.sched is None else self.sched[t]
+                train_loss[t] = torch.sum(self.sc_w[t] * torch.tensor([float(v) for v in lh[t][S]]))
+            elif self.sched is not None:   # the sampled clients' weights and losses, ascending client id
                 train_loss[t] = torch.sum(self.q_host[t] * torch.tensor([float(v) for v in lh[t][self.sched[t]]]))
             else:
                 train_loss[t] = torch.sum(pt * torch.tensor([float(v) for v in lh[t]]))   # tools.py:344 / 434
@@ -686,6 +781,10 @@ class Federation:
                               ld=self.ld)
             if self.W_hist is not None:
                 self.stats['W_rounds'] = self.W_hist[:R, :, :D].cpu().numpy()
+            if self.scaffold:
+                self.stats['c_global'] = self.c_var[:, :D].detach().clone()
+                if self.c_hist is not None:
+                    self.stats['c_rounds'] = self.c_hist[:R, :, :D].cpu().numpy()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -705,6 +804,28 @@ class Federation:
                     hist = hist[self.inv].permute(1, 0, 2)
                 _local_eval_stats(self.stats, which, hist, self.ns)
         return train_loss, test_loss, test_acc
+
+
+def Scaffold(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+             batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, server_lr=1.0,
+             weighting='size', stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """SCAFFOLD (Karimireddy et al., ICML 2020, option II; not in the reference): FedAvg's positional
+    list, clients always parallel.  Every local step adds d = c - c_i to the gradient, every trained
+    client leaves c_i+ = c_i - c + (x - y_i) / (K_i lr) behind (fs_local_train_scaffold), and the
+    server folds the sampled models twice from one pass (fs_aggregate_scaffold):
+    x += server_lr * sum_S (p_k / sum_S p) (y_k - x) and c = (1 - sum_S p) c + sum_S p_k (x - y_k) / (K_k lr),
+    which keeps c = sum_j p_j c_j over all clients.  ``weighting='size'``: p_i = n_i / n (the project's
+    convention); ``'uniform'``: p_i = 1 / N, the paper's Algorithm 1 literally.  The global generator
+    is consumed exactly as by ``FedAvg(clients='parallel')`` with the same ``participation``;
+    ``train_loss[t] = sum_S (p_k / sum_S p) loss_k``.  ``stats['c_global']`` [C, D]; with
+    ``stats['trace']`` also ``stats['c_rounds']`` [R, C, D].  ValueError for ``prox=True``,
+    ``type='regression'`` and ``batch_size > 64``; NotImplementedError over more than one
+    torch.distributed rank.  ``mu`` is ignored."""
+    _check_scaffold(type, prox, batch_size, weighting, server_lr)
+    return _run('scaffold', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                False, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed, server_lr=server_lr,
+                weighting=weighting)
 
 
 def _run(algo, *args, stats=None, verbose=True, options=None, participation=None, sample_seed=0, **kw):
