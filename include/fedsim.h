@@ -395,7 +395,47 @@ int fs_aggregate_scaffold(const float* d_W_all, int64_t stride, const int32_t* d
                           float* d_ws, int64_t ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * Test evaluation.  Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
+ * FedOpt server optimizers (Reddi et al., ICLR 2021, Algorithm 2: FedAdagrad / FedAdam / FedYogi;
+ * server momentum FedAvgM, Hsu et al. 2019).  Additive to ABI 23: two new entry points, no new
+ * field in fs_tuning or fs_plan_desc, FS_ABI_VERSION unchanged.
+ *
+ * fs_aggregate_opt: the fold of the updates of the M rows d_sel (NULL: rows 0..M-1) of d_W_all
+ * with the optimizer step fused onto its end, d_W_g, d_m and d_v [len] updated in place.  With
+ * x = d_W_g, m = d_m, v = d_v on entry, k ascending, every operation rounded separately:
+ *     delta = sum_k fl(q_k * fl(W_k - x)),     d2 = fl(delta*delta)
+ *   FS_OPT_AVGM     m' = fl(fl(beta1*m) + delta),   x' = fl(x + fl(eta*m'));  d_v is not read and
+ *                   may be NULL
+ *   the others      m' = fl(fl(beta1*m) + fl(omb1*delta))
+ *   FS_OPT_ADAGRAD  v' = fl(v + d2)
+ *   FS_OPT_ADAM     v' = fl(fl(beta2*v) + fl(omb2*d2))
+ *   FS_OPT_YOGI     v' = fl(v - fl(fl(omb2*d2) * s)),  s = sgn(fl(v - d2)) in {-1, 0, +1}
+ *                   x' = fl(x + fl(fl(eta*m') / fl(sqrtf(v') + tau)))
+ * with the correctly rounded IEEE quotient and square root and no bias correction (as the paper).
+ * omb1 and omb2 are the caller's f32(1 - beta), computed in float64: the host decides their
+ * rounding once.  delta is folded exactly as fs_aggregate_nova folds mode FS_NOVA_UPDATES before
+ * it adds its base -- the first term of a range is the term itself; regimes are fs_aggregate's,
+ * chosen by M with the same `chunks`, d_ws and ws_floats (one partial per chunk): the exact left
+ * fold for M < 16 or chunks == 1, else the same sub-ranges / chunks and stage-2 tree -- so
+ * FS_OPT_AVGM with beta1 = 0, eta = 1 leaves in d_W_g bitwise what mode FS_NOVA_UPDATES returns
+ * with base d_W_g.  The step runs once per element, in the thread that writes the position; a
+ * position's x, m and v are read by the workgroup that writes them, before it writes.  Rows
+ * outside d_sel are never read.  (M + 3)*len floats read and 3*len written (FS_OPT_AVGM: M + 2
+ * and 2).  No atomics, no cross-workgroup wait, no allocation; asynchronous on `stream`.
+ * FS_EINVAL for M < 1, len or stride no multiple of 4, stride < len, a rule outside 1..4, a null
+ * pointer the rule needs (d_sel and d_ws may be NULL), tau <= 0 for rules 2..4 (a padding column
+ * has delta = 0 and its step must be 0 / positive) or any two of d_W_g, d_m, d_v equal; nothing
+ * is written then.
+ * ------------------------------------------------------------------------- */
+#define FS_OPT_AVGM    1
+#define FS_OPT_ADAGRAD 2
+#define FS_OPT_ADAM    3
+#define FS_OPT_YOGI    4
+int fs_aggregate_opt(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int rule,
+                     float eta, float beta1, float omb1, float beta2, float omb2, float tau, int M, int64_t len,
+                     float* d_W_g, float* d_m, float* d_v, float* d_ws, int64_t ws_floats, int chunks, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
  * d_ws needs fs_eval_ws_doubles(n) doubles.
@@ -802,6 +842,22 @@ int fs_plan_set_nova(fs_plan* plan, int mode, const float* d_b, float te, float 
  * a null pointer with on = 1, or turning it on while the plan holds a pending evaluation
  * (fs_plan_eval_flush first). */
 int fs_plan_set_scaffold(fs_plan* plan, int on, float* d_c, float* d_ci, const float* d_r, float cs);
+
+/* (additive to ABI 23) A server optimizer on this plan's AGGREGATE phase.  Host state read when
+ * the next round call enqueues, as fs_plan_set_nova's.  rule FS_OPT_AVGM .. FS_OPT_YOGI: AGGREGATE
+ * launches fs_aggregate_opt with d_q = the round's weights (d_p, the override, or the subset
+ * call's d_q, already p_k / sum_S p), d_sel = the subset's ids or NULL, d_W_g in place, the
+ * moments d_m and d_v [C][ld] in place, the plan's aggregation workspace and chunks, and the
+ * pending finaliser of a deferred evaluation.  TRAIN is unchanged: every training form, the prox
+ * term, loss = 1, B > 64, subset rounds, chunked shuffles and the fused deferred evaluation work
+ * as without it.  d_m and d_v are read and written asynchronously by those launches: keep them
+ * alive (d_v may be NULL for FS_OPT_AVGM).  rule 0 restores the plain aggregate (the other
+ * arguments are ignored).  FS_EINVAL for a chained plan (a chained client's W_j - W_g holds its
+ * predecessors' work), a nova mode other than 0, SCAFFOLD on, null moments, tau <= 0 for rules
+ * 2..4, or another rule; fs_plan_set_nova and fs_plan_set_scaffold refuse in turn while a rule is
+ * set. */
+int fs_plan_set_server_opt(fs_plan* plan, int rule, float* d_m, float* d_v, float eta, float beta1, float omb1,
+                           float beta2, float omb2, float tau);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

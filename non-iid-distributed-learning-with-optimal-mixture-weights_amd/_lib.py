@@ -50,6 +50,12 @@ _SIGS = {
     'fs_aggregate_scaffold': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'fs_plan_set_scaffold': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
+    # FedOpt server optimizers (additive to ABI 23)
+    'fs_aggregate_opt': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    'fs_plan_set_server_opt': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_float]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -113,7 +119,9 @@ ABI_VERSION = 23
 
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 NOVA_REFERENCE, NOVA_UPDATES = 1, 2   # fs_aggregate_nova / fs_plan_set_nova modes (ABI 23)
-G_PAIR = 256             # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
+OPT_AVGM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 1, 2, 3, 4   # fs_aggregate_opt / fs_plan_set_server_opt rules
+OPT_RULES = {'avgm': OPT_AVGM, 'adagrad': OPT_ADAGRAD, 'adam': OPT_ADAM, 'yogi': OPT_YOGI}
+G_PAIR = 256            # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
 G_TEAMS = 512            # fs_local_train_plan: G | G_TEAMS = the team form at width G (ABI 13)
 LT_KERNELS = {1: 'single', 2: 'split', 3: 'dbuf', 4: 'pair', 5: 'pipe', 6: 'teams', 7: 'mb',
               8: 'wide'}   # fs_local_train_last_kernel (ABI 15; mb: 16; wide: 21)
@@ -341,6 +349,7 @@ KERNEL_SOURCES = {
     'local_train_scaffold': ('local_train_scaffold.hip', 'scaffold.h', 'common.h'),
     'aggregate_scaffold': ('aggregate_scaffold.hip', 'aggregate.hip', 'aggregate_sel.h', 'scaffold.h', 'finalize.h',
                            'common.h'),
+    'aggregate_opt': ('aggregate_opt.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
 }
 
 

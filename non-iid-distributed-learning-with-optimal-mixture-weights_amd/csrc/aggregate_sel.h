@@ -28,4 +28,10 @@ int aggregate_nova_launch(const float* d_W_all, int64_t stride, const int32_t* d
                           float* d_W_bar, float* d_ws, int64_t ws_floats, int chunks, const EvalFinalize* fin,
                           hipStream_t st);
 
+// fs_aggregate_opt (aggregate_opt.hip) with an optional finaliser, as the three above
+int aggregate_opt_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int rule,
+                         float eta, float beta1, float omb1, float beta2, float omb2, float tau, int M, int64_t len,
+                         float* d_W_g, float* d_m, float* d_v, float* d_ws, int64_t ws_floats, int chunks,
+                         const EvalFinalize* fin, hipStream_t st);
+
 }  // namespace fs

@@ -33,6 +33,10 @@
 // (local_train_scaffold.hip; the plan's G and workspace are ignored) and AGGREGATE launches
 // fs_aggregate_scaffold (aggregate_scaffold.hip), which updates d_W_g and the server variate from one
 // pass over the round's rows.  A deferred evaluation is never fused while it is on.
+//
+// FedOpt (additive to ABI 23, fs_plan_set_server_opt): AGGREGATE launches fs_aggregate_opt
+// (aggregate_opt.hip), the mode-2 fold with a server optimizer step on its end, updating d_W_g and
+// the moments in place.  TRAIN is untouched, and the deferred evaluation's finaliser rides on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -176,6 +180,11 @@ struct fs_plan {
   float* sc_ci = nullptr;             // [N][C][ld] client variates
   const float* sc_r = nullptr;        // [N], or [M] of a subset round
   float sc_cs = 0.f;
+  // fs_plan_set_server_opt: AGGREGATE is fs_aggregate_opt with this rule (0: none)
+  int opt_rule = 0;
+  float* opt_m = nullptr;             // [C][ld] first moment
+  float* opt_v = nullptr;             // [C][ld] second moment (AVGM: unused)
+  float opt_eta = 0.f, opt_beta1 = 0.f, opt_omb1 = 0.f, opt_beta2 = 0.f, opt_omb2 = 0.f, opt_tau = 0.f;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -822,7 +831,11 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       if (rc == FS_OK)
         rc = fs::aggregate_scaffold_launch(d.d_W_out, len, sel, pw, p->sc_r, p->sc_cs, M, len, d.d_W_g, p->sc_c,
                                            d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, st);
-    } else if (p->nova_mode)
+    } else if (p->opt_rule)
+      rc = fs::aggregate_opt_launch(d.d_W_out, len, sel, pw, p->opt_rule, p->opt_eta, p->opt_beta1, p->opt_omb1,
+                                    p->opt_beta2, p->opt_omb2, p->opt_tau, M, len, d.d_W_g, p->opt_m, p->opt_v,
+                                    d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
+    else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
     else if (sub)
@@ -856,6 +869,8 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   FS_REQUIRE(mode != FS_NOVA_REFERENCE || d_b, "mode 1 needs d_b");
   FS_REQUIRE(!(mode == FS_NOVA_UPDATES && p->d.chained),
              "mode 2 needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  FS_REQUIRE(mode == 0 || p->opt_rule == 0,
+             "a FedNova aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -885,6 +900,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(p->d.B <= 64, "SCAFFOLD needs batch_size <= 64");
   FS_REQUIRE(!p->d.prox, "the prox term is not supported together with SCAFFOLD");
   FS_REQUIRE(p->nova_mode == 0, "SCAFFOLD and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "SCAFFOLD and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -892,6 +908,38 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   p->sc_ci = d_ci;
   p->sc_r = d_r;
   p->sc_cs = cs;
+  return FS_OK;
+}
+
+// Additive to ABI 23: a server optimizer on the AGGREGATE phases enqueued from now on (host
+// state, read when a round call enqueues, as fs_plan_set_nova's).  rule FS_OPT_*: AGGREGATE launches
+// fs_aggregate_opt with q = the round's weights, d_W_g and the moments d_m / d_v [C][ld] in place
+// and the pending finaliser; TRAIN is unchanged.  rule 0: the plain aggregate again.
+extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d_v, float eta, float beta1, float omb1,
+                                      float beta2, float omb2, float tau) {
+  FS_REQUIRE(p, "bad arguments");
+  if (rule == 0) {
+    p->opt_rule = 0;
+    p->opt_m = p->opt_v = nullptr;
+    return FS_OK;
+  }
+  FS_REQUIRE(rule >= FS_OPT_AVGM && rule <= FS_OPT_YOGI, "rule must be 0 or FS_OPT_AVGM .. FS_OPT_YOGI");
+  FS_REQUIRE(d_m && (rule == FS_OPT_AVGM || d_v), "null moments");
+  FS_REQUIRE(d_m != d_v && d_m != p->d.d_W_g && d_v != p->d.d_W_g, "d_W_g, d_m and d_v must be different buffers");
+  FS_REQUIRE(rule == FS_OPT_AVGM || tau > 0.f, "tau must be > 0");
+  FS_REQUIRE(!p->d.chained,
+             "a server optimizer needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  FS_REQUIRE(p->nova_mode == 0, "a server optimizer and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "a server optimizer and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  p->opt_rule = rule;
+  p->opt_m = d_m;
+  p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
+  p->opt_eta = eta;
+  p->opt_beta1 = beta1;
+  p->opt_omb1 = omb1;
+  p->opt_beta2 = beta2;
+  p->opt_omb2 = omb2;
+  p->opt_tau = tau;
   return FS_OK;
 }
 

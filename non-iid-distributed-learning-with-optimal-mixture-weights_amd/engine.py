@@ -456,6 +456,28 @@ class RoundPlan:
                    'fs_plan_set_scaffold')
         self._scaffold = (c, ci, r)
 
+    def set_server_opt(self, rule, m=None, v=None, eta=1.0, beta1=0.0, omb1=1.0, beta2=0.0, omb2=1.0, tau=1.0):
+        """fs_plan_set_server_opt: a FedOpt server optimizer on the AGGREGATE phases enqueued from now
+        on -- ``rule`` 0 the plain aggregate, ``_lib.OPT_AVGM`` .. ``_lib.OPT_YOGI`` (or their names,
+        ``_lib.OPT_RULES``) fs_aggregate_opt with the round's weights as ``q``, updating ``W_g`` and the
+        moments ``m`` / ``v`` [C, ld] in place.  TRAIN is unchanged.  Float32 device tensors the
+        launches read and write asynchronously (the plan keeps the last ones alive); the scalars are
+        float32 values (``tools.server_opt_scalars``)."""
+        rule = _lib.OPT_RULES.get(rule, rule) if isinstance(rule, str) else rule
+        if not rule:
+            _lib.check(_lib.lib().fs_plan_set_server_opt(self._h, 0, None, None, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0),
+                       'fs_plan_set_server_opt')
+            self._server_opt = None
+            return
+        n = self._desc.C * self._desc.ld
+        for x in (m, v):
+            if x is not None and not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n):
+                raise ValueError('set_server_opt: m and v must be contiguous float32 device tensors of C * ld floats')
+        _lib.check(_lib.lib().fs_plan_set_server_opt(self._h, int(rule), _lib.ptr(m), _lib.ptr(v), float(eta),
+                                                     float(beta1), float(omb1), float(beta2), float(omb2), float(tau)),
+                   'fs_plan_set_server_opt')
+        self._server_opt = (m, v)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -571,6 +593,39 @@ class Aggregator:
                                                     _lib.ptr(c), _lib.ptr(self.ws), self.ws.numel(), int(self.chunks),
                                                     _lib.stream_ptr()), 'fs_aggregate_scaffold')
         return W_g, c
+
+    def run_opt(self, W_all, q, rule, W_g, m, v=None, eta=1.0, beta1=0.0, omb1=1.0, beta2=0.0, omb2=1.0, tau=1.0,
+                sel=None, check=True):
+        """fs_aggregate_opt: the FedOpt server step from one pass over the rows ``sel`` of ``W_all``
+        (None: rows 0..len(q)-1), in place with x = ``W_g`` on entry: ``delta = sum_k q_k*(W_k - x)``
+        folded as ``run_nova`` mode 2 folds it (the regimes of ``run`` at len(q) clients), then the
+        step of ``rule`` (``_lib.OPT_AVGM`` .. ``_lib.OPT_YOGI`` or a name of ``_lib.OPT_RULES``) on ``W_g``
+        and the moments ``m``, ``v`` (None for avgm).  The scalars are passed as float32 values
+        (``tools.server_opt_scalars``).  ``check`` as in ``run_sel``."""
+        M = int(q.numel())
+        rule = _lib.OPT_RULES.get(rule, rule) if isinstance(rule, str) else rule
+
+        def f32(x):
+            return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if not (f32(q) and M >= 1 and all(x is None or (f32(x) and x.numel() >= self.len) for x in (W_g, m, v))):
+            raise ValueError('run_opt: q (float32, non-zero length), W_g, m and v (float32, len) must be contiguous '
+                             'device tensors')
+        if sel is not None:
+            if not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == M):
+                raise ValueError('run_opt: sel must be a contiguous int32 device tensor as long as q')
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('run_opt: q is longer than W_all has rows')
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_opt: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_opt(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                               _lib.ptr(q), int(rule), float(eta), float(beta1), float(omb1),
+                                               float(beta2), float(omb2), float(tau), M, self.len, _lib.ptr(W_g),
+                                               _lib.ptr(m), _lib.ptr(v), _lib.ptr(self.ws), self.ws.numel(),
+                                               int(self.chunks), _lib.stream_ptr()), 'fs_aggregate_opt')
+        return W_g, m, v
 
 
 class Evaluator:

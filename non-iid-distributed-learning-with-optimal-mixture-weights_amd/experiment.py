@@ -54,7 +54,8 @@ NAMES = ['CL', 'DL', 'FedAMW_OneShot', 'FedAvg', 'FedProx', 'FedAMW']
 # exp.py:124 leaves its FedNova call commented out: it runs only when ``algos`` names it, and its
 # rows are then appended after the six above (the default result layout is unchanged)
 # Scaffold (not in the reference) likewise: its row comes after FedNova's
-EXTRA = ['FedNova', 'Scaffold']
+# the FedOpt server optimizers (not in the reference) after Scaffold's, in this order
+EXTRA = ['FedNova', 'Scaffold', 'FedAvgM', 'FedAdagrad', 'FedAdam', 'FedYogi']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -92,7 +93,7 @@ def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None
 def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batch_size=32, n_repeats=1,
         alpha_Dirk=0.01, data_dir='../FedAMW/datasets/', result_dir='./results', save=True, clients='sequential',
         algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None, participation=None,
-        sample_seed=0):
+        sample_seed=0, server_lr=None, server_beta1=0.9, server_beta2=0.99, server_tau=1e-3):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
@@ -216,6 +217,27 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             keep_participants('Scaffold', st)
             k = names.index('Scaffold')
             train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        for name in ('FedAvgM', 'FedAdagrad', 'FedAdam', 'FedYogi'):
+            if name not in algos:
+                continue
+            # FedAvg's arguments; clients are always parallel; server_lr None: the rule's default
+            st = ce(name, False)
+            if participation is not None:
+                st = st or {}
+            opar = dict(kw) if participation is None else dict(participation=participation, sample_seed=sample_seed,
+                                                               **kw)
+            opar.update(beta1=server_beta1, tau=server_tau)
+            if server_lr is not None:
+                opar['server_lr'] = server_lr
+            if name == 'FedAvgM':
+                del opar['tau']
+            else:
+                opar['beta2'] = server_beta2
+            r = timed(name, lambda: getattr(tools, name)(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False,
+                                                         0, Round, stats=st, **opar))
+            keep_participants(name, st)
+            k = names.index(name)
+            train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -248,8 +270,8 @@ def main(argv=None):
     ap.add_argument('--result-dir', default='./results')
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES),
-                    help='comma-separated; FedNova (exp.py:124, commented out there) and Scaffold run only when named '
-                         'here')
+                    help='comma-separated; FedNova (exp.py:124, commented out there), Scaffold, FedAvgM, FedAdagrad, '
+                         'FedAdam and FedYogi run only when named here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -257,14 +279,22 @@ def main(argv=None):
                     help="score the round's global model / every client's own model on each client's own rows")
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
-                         'Applies to the FedAvg, FedProx, FedNova and Scaffold calls only, which then run with parallel clients '
+                         'Applies to the FedAvg, FedProx, FedNova, Scaffold and server-optimizer (FedAvgM, FedAdagrad, '
+                         'FedAdam, FedYogi) calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')
+    ap.add_argument('--server-lr', type=float, default=None,
+                    help='FedAvgM / FedAdagrad / FedAdam / FedYogi: the server learning rate (default: the rule\'s own)')
+    ap.add_argument('--server-beta1', type=float, default=0.9, help='server momentum / first-moment decay')
+    ap.add_argument('--server-beta2', type=float, default=0.99, help='second-moment decay (FedAdam, FedYogi)')
+    ap.add_argument('--server-tau', type=float, default=1e-3, help='adaptivity of the adaptive server optimizers')
     a = ap.parse_args(argv)
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
               a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval,
-              local_eval=a.local_eval, participation=a.participation, sample_seed=a.sample_seed)
+              local_eval=a.local_eval, participation=a.participation, sample_seed=a.sample_seed,
+              server_lr=a.server_lr, server_beta1=a.server_beta1, server_beta2=a.server_beta2,
+              server_tau=a.server_tau)
     for k, name in enumerate(out['name']):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

@@ -359,6 +359,37 @@ def scaffold_round_coefficients(ns, S, epoch, batch_size, lr, server_lr=1.0, wei
     return q, r, cs, (p / psum).astype(np.float32)
 
 
+SERVER_OPTS = ('avgm', 'adagrad', 'adam', 'yogi')
+# the default server learning rates: 1 for momentum (FedAvgM's usual setting); 0.1 = 10^-1 for the
+# adaptive rules, a point of the paper's grid {10^-3, 10^-2.5, ..., 10^1} -- a default, not a tuned value
+SERVER_LR_DEFAULT = {'avgm': 1.0, 'adagrad': 0.1, 'adam': 0.1, 'yogi': 0.1}
+
+
+def _check_server_opt(server_opt, server_lr, beta1, beta2, tau):
+    """FedOpt's keyword checks (host only: before any device is touched)."""
+    if server_opt not in SERVER_OPTS:
+        raise ValueError("server_opt must be one of 'avgm', 'adagrad', 'adam', 'yogi'")
+    if server_lr is not None and not float(server_lr) > 0.0:
+        raise ValueError('server_lr must be > 0')
+    if not float(tau) > 0.0:
+        raise ValueError('tau must be > 0')
+    for name, b in (('beta1', beta1), ('beta2', beta2)):
+        if not 0.0 <= float(b) < 1.0:
+            raise ValueError('%s must be in [0, 1)' % name)
+
+
+def server_opt_scalars(server_opt, server_lr=None, beta1=0.9, beta2=0.99, tau=1e-3):
+    """The host scalars of fs_aggregate_opt, computed in float64 and rounded once to float32:
+    (rule, eta, beta1, omb1, beta2, omb2, tau) with omb = f32(1 - beta), the subtraction in float64
+    on the caller's beta (not on its float32 rounding).  ``server_lr`` None: the rule's default
+    (``SERVER_LR_DEFAULT``).  Returns the rule id (``_lib.OPT_*``) and six ``np.float32``."""
+    _check_server_opt(server_opt, server_lr, beta1, beta2, tau)
+    eta = SERVER_LR_DEFAULT[server_opt] if server_lr is None else float(server_lr)
+    f = np.float32
+    return (_lib.OPT_RULES[server_opt], f(eta), f(float(beta1)), f(1.0 - float(beta1)), f(float(beta2)),
+            f(1.0 - float(beta2)), f(float(tau)))
+
+
 class Federation:
     """One algorithm call split into setup / rounds / results (bench.py drives the
     rounds one at a time through the same code path as the drop-ins)."""
@@ -366,7 +397,20 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size'):
+                 server_lr=1.0, weighting='size', server_opt=None):
+        self.fedopt = algo == 'fedopt'
+        if self.fedopt:
+            # server_opt: dict(rule=, server_lr=, beta1=, beta2=, tau=, v0=) (tools.FedOpt)
+            so = dict(server_opt or {})
+            self.opt_v0 = so.pop('v0', None)
+            so.setdefault('rule', 'adam')
+            self.opt_tau = float(so.get('tau', 1e-3))      # the caller's tau: v0 = tau^2 in float64, rounded once
+            self.opt_scalars = server_opt_scalars(so.pop('rule'), **so)
+            if self.opt_v0 is not None and not float(self.opt_v0) >= 0.0:
+                raise ValueError('v0 must be >= 0')
+            if clients != 'parallel':
+                raise ValueError("FedOpt needs clients='parallel': a chained client's W_j - W_g contains its "
+                                 "predecessors' work")
         if algo == 'fednova':
             _check_nova(variant, clients)
         self.scaffold = algo == 'scaffold'
@@ -396,8 +440,9 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold'):
-                raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova and Scaffold only')
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt'):
+                raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold and '
+                                          'FedOpt only')
             if self.chained:
                 raise ValueError("participation needs clients='parallel': every sampled client starts from the "
                                  "round's global model (clients='sequential' chains all clients)")
@@ -408,6 +453,9 @@ class Federation:
             raise NotImplementedError('FedNova over more than one torch.distributed rank is not implemented')
         if self.scaffold and nranks > 1:
             raise NotImplementedError('Scaffold over more than one torch.distributed rank is not implemented')
+        if self.fedopt and nranks > 1:
+            # (delta would need its all-reduce before the nonlinear step)
+            raise NotImplementedError('FedOpt over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -580,6 +628,17 @@ class Federation:
         # keeps per-round shuffles (its validation shuffles are double-buffered per round).
         if self.nova is not None and self.sched is None:
             self.plan.set_nova(*self.nova)
+        if self.fedopt:
+            # FedOpt: FedAvg's round with fs_aggregate_opt as its aggregate.  m0 = 0, v0 = tau^2 (the
+            # paper's initialisation) unless given; the scalars do not change with the round
+            tau = self.opt_tau
+            self.opt_m = torch.zeros(C, ld, device=dev, dtype=torch.float32)
+            self.opt_v = torch.full((C, ld), tau * tau if self.opt_v0 is None else float(self.opt_v0), device=dev,
+                                    dtype=torch.float32)
+            self.plan.set_server_opt(self.opt_scalars[0], self.opt_m, self.opt_v, *self.opt_scalars[1:])
+            trace = stats is not None and stats.get('trace')
+            self.m_hist = torch.empty(R, C, ld, device=dev) if trace else None
+            self.v_hist = torch.empty(R, C, ld, device=dev) if trace else None
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -729,6 +788,9 @@ class Federation:
             self.W_hist[t].copy_(self.W_g)
         if self.scaffold and self.c_hist is not None:
             self.c_hist[t].copy_(self.c_var)
+        if self.fedopt and self.m_hist is not None:
+            self.m_hist[t].copy_(self.opt_m)
+            self.v_hist[t].copy_(self.opt_v)
         self.t += 1
         if self.chunk > 1:
             if t % self.chunk == 0 and t >= self.chunk:      # chunk c started: prepare chunk c + 1
@@ -785,6 +847,12 @@ class Federation:
                 self.stats['c_global'] = self.c_var[:, :D].detach().clone()
                 if self.c_hist is not None:
                     self.stats['c_rounds'] = self.c_hist[:R, :, :D].cpu().numpy()
+            if self.fedopt:
+                self.stats['server_m'] = self.opt_m[:, :D].detach().clone()
+                self.stats['server_v'] = self.opt_v[:, :D].detach().clone()
+                if self.m_hist is not None:
+                    self.stats['server_m_rounds'] = self.m_hist[:R, :, :D].cpu().numpy()
+                    self.stats['server_v_rounds'] = self.v_hist[:R, :, :D].cpu().numpy()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -872,6 +940,61 @@ def FedNova(X_train, y_train, X_test, y_test, type='classification', num_classes
     return _run('fednova', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
                 prox, mu, lambda_reg_if, lambda_reg, round, None, clients, stats=stats, verbose=verbose,
                 options=options, participation=participation, sample_seed=sample_seed, variant=variant)
+
+
+def FedOpt(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+           batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, server_opt='adam',
+           server_lr=None, beta1=0.9, beta2=0.99, tau=1e-3, v0=None, stats=None, verbose=True, options=None,
+           participation=None, sample_seed=0):
+    """Adaptive federated optimization (Reddi et al., ICLR 2021, Algorithm 2) and server momentum
+    (FedAvgM, Hsu et al. 2019); not in the reference.  FedAvg's positional list, clients always
+    parallel.  Local training is FedAvg's launch unchanged -- both tasks, ``prox=True``, any
+    ``batch_size`` the task's trainer accepts, ``participation`` -- and only the server step differs
+    (fs_aggregate_opt): with delta = sum_S (p_k / sum_S p) (W_k - x),
+    ``'avgm'``: m = beta1 m + delta, x += server_lr m;  the others m = beta1 m + (1 - beta1) delta,
+    ``'adagrad'``: v += delta^2;  ``'adam'``: v = beta2 v + (1 - beta2) delta^2;
+    ``'yogi'``: v -= (1 - beta2) delta^2 sign(v - delta^2);  x += server_lr m / (sqrt(v) + tau),
+    without bias correction, as the paper.  m0 = 0 and ``v0=None`` means tau^2 (the paper's
+    initialisation).  ``server_lr=None`` takes the rule's default (``SERVER_LR_DEFAULT``: 1 for
+    'avgm'; 0.1 for the adaptive rules, a point of the paper's grid -- a default, not a tuned value).
+    The host scalars are ``server_opt_scalars``'.  The global generator is consumed exactly as by
+    ``FedAvg(clients='parallel')`` with the same ``participation``, and ``train_loss`` is FedAvg's.
+    ``stats['server_m']`` / ``stats['server_v']`` [C, D]; with ``stats['trace']`` also
+    ``stats['server_m_rounds']`` / ``stats['server_v_rounds']`` [R, C, D] next to ``W_rounds``.
+    ValueError for an unknown rule, ``tau <= 0``, a beta outside [0, 1) and ``server_lr <= 0``;
+    NotImplementedError over more than one torch.distributed rank."""
+    _check_server_opt(server_opt, server_lr, beta1, beta2, tau)
+    return _run('fedopt', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed,
+                server_opt=dict(rule=server_opt, server_lr=server_lr, beta1=beta1, beta2=beta2, tau=tau, v0=v0))
+
+
+def FedAvgM(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, server_lr=1.0,
+            beta1=0.9, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """``FedOpt(server_opt='avgm')``: server momentum ``beta1``, m = beta1 m + delta, x += server_lr m."""
+    return FedOpt(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                  lambda_reg_if, lambda_reg, round, server_opt='avgm', server_lr=server_lr, beta1=beta1, stats=stats,
+                  verbose=verbose, options=options, participation=participation, sample_seed=sample_seed)
+
+
+def _adaptive(rule):
+    def f(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+          batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *,
+          server_lr=SERVER_LR_DEFAULT[rule], beta1=0.9, beta2=0.99, tau=1e-3, v0=None, stats=None, verbose=True,
+          options=None, participation=None, sample_seed=0):
+        return FedOpt(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                      lambda_reg_if, lambda_reg, round, server_opt=rule, server_lr=server_lr, beta1=beta1, beta2=beta2,
+                      tau=tau, v0=v0, stats=stats, verbose=verbose, options=options, participation=participation,
+                      sample_seed=sample_seed)
+    f.__name__ = f.__qualname__ = 'Fed' + rule.capitalize()
+    f.__doc__ = ("``FedOpt(server_opt=%r)`` (Reddi et al., ICLR 2021).  ``server_lr`` defaults to 0.1, a point of the "
+                 "paper's grid: a default, not a tuned value (``beta2`` is unused by 'adagrad')." % rule)
+    return f
+
+
+FedAdagrad, FedAdam, FedYogi = _adaptive('adagrad'), _adaptive('adam'), _adaptive('yogi')
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
