@@ -435,6 +435,48 @@ int fs_aggregate_opt(const float* d_W_all, int64_t stride, const int32_t* d_sel,
                      float* d_W_g, float* d_m, float* d_v, float* d_ws, int64_t ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * q-FedAvg (q-FFL; Li, Sanjabi, Beirami, Smith, ICLR 2020).  Additive to ABI 23: four new entry
+ * points, no new field in fs_tuning or fs_plan_desc, FS_ABI_VERSION unchanged.
+ *
+ * fs_aggregate_qffl: the q-FFL server step from ONE pass over the M rows d_sel (NULL: rows
+ * 0..M-1) of d_W_all: the weighted fold of the updates and every update's squared norm from the
+ * same loads.  With x = d_W_g on entry, k ascending, every float operation rounded separately:
+ *     d_S    = sum_k fl(u_k * fl(W_k - x))           folded exactly as fs_aggregate_opt folds its
+ *              delta (the regimes of fs_aggregate at M rows, the same `chunks`, d_ws, ws_floats;
+ *              the first term of a range is the term itself): bitwise the d_m that
+ *              FS_OPT_AVGM with beta1 = 0 leaves with q = u
+ *     d_n[k] = sum_i fl(W_k[i] - x[i])^2             the same differences, from the same load; in
+ *              float only inside one wave's share of a row (the square, the thread's 4 elements,
+ *              at most 6 levels across the wave: at most 10 roundings), in double in a fixed order
+ *              above that: within 16 * 2^-24 relative of the exact sum of the float differences'
+ *              squares whatever len, and the same bits on every call
+ *     U = sum_k (double)u_k,  G = sum_k (double)g_k * d_n[k],  H = Lc * U + G     (double, IEEE)
+ *     coef   = (float)(Lc / H);  0 when H is not finite or <= 0, and d_W_g is then left as it is
+ *     d_W_g  = fl(x + fl(coef * d_S));               d_hc = {H, (double)coef}
+ * (M + 1)*len floats read by the pass; the two small launches after it touch len- and M-sized data
+ * and the partial table only.  d_nws: fs_aggregate_qffl_ws_doubles(M, len) doubles of workspace
+ * (the table of the waves' float shares; it holds nothing between calls).  Rows outside d_sel are
+ * never read.  No atomics, no cross-workgroup wait, no allocation, no host synchronisation;
+ * asynchronous on `stream`.
+ * FS_EINVAL for M < 1, len or stride no multiple of 4, stride < len, a null pointer (d_sel and
+ * d_ws may be NULL), Lc <= 0 or not finite, nws_doubles too small or d_S == d_W_g; nothing is
+ * written then.
+ *
+ * fs_qffl_coef: the coefficients of a round from the losses fs_eval_clients left on the device
+ * (d_F2 [N][2], the loss at [k][0]), one small launch: with Ft = d_F2[2 * row_k] + 1e-10,
+ * row_k = d_sel[k] (NULL: k), in double and rounded once to float
+ *     d_u[k] = d_p[k] * Ft^q            d_g[k] = d_p[k] * q * Ft^(q-1) * L^2
+ * and q = 0 gives d_u = d_p, d_g = 0 exactly.  FS_EINVAL for q < 0, L <= 0, M < 1 or a null
+ * pointer (d_sel may be NULL).
+ * ------------------------------------------------------------------------- */
+int64_t fs_aggregate_qffl_ws_doubles(int M, int64_t len);
+int fs_aggregate_qffl(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_u, const float* d_g,
+                      double Lc, int M, int64_t len, float* d_W_g, float* d_S, double* d_n, double* d_hc, float* d_ws,
+                      int64_t ws_floats, int chunks, double* d_nws, int64_t nws_doubles, void* stream);
+int fs_qffl_coef(const double* d_F2, const int32_t* d_sel, const float* d_p, double q, double L, int M, float* d_u,
+                 float* d_g, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -858,6 +900,24 @@ int fs_plan_set_scaffold(fs_plan* plan, int on, float* d_c, float* d_ci, const f
  * set. */
 int fs_plan_set_server_opt(fs_plan* plan, int rule, float* d_m, float* d_v, float eta, float beta1, float omb1,
                            float beta2, float omb2, float tau);
+
+/* (additive to ABI 23) q-FedAvg on this plan's AGGREGATE phase.  Host state read when the next
+ * round call enqueues, as fs_plan_set_server_opt's.  on = 1: AGGREGATE launches fs_aggregate_qffl
+ * with d_u = the round's weights (d_p, the override, or the subset call's d_q: the caller puts
+ * fs_qffl_coef's u there), d_g ([N]; [M] of a subset round), Lc, d_sel = the subset's ids or NULL,
+ * d_W_g in place, the outputs d_S [C][ld], d_n ([N] / [M]) and d_hc [2], the plan's aggregation
+ * workspace and chunks, d_nws (the largest fs_aggregate_qffl_ws_doubles(M, C * ld) over 1 <= M <= N
+ * doubles: the table is largest at the last M of a regime of the fold, not always at N) and the
+ * pending finaliser of a deferred evaluation.  TRAIN is unchanged: every training form, the prox term,
+ * loss = 1, B > 64, subset rounds, chunked shuffles and the fused deferred evaluation work as
+ * without it.  Lc follows the round's lr: call again before each round (allowed while on).  The
+ * buffers are read and written asynchronously by those launches: keep them alive.  on = 0 restores
+ * the plain aggregate (the other arguments are ignored).  FS_EINVAL for a chained plan, a nova mode
+ * other than 0, SCAFFOLD on, a server-optimizer rule set, a null pointer, Lc <= 0 or not finite,
+ * d_S == d_W_g or a d_nws too small; fs_plan_set_nova, fs_plan_set_scaffold and
+ * fs_plan_set_server_opt refuse in turn while it is on. */
+int fs_plan_set_qffl(fs_plan* plan, int on, const float* d_g, double Lc, float* d_S, double* d_n, double* d_hc,
+                     double* d_nws, int64_t nws_doubles);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

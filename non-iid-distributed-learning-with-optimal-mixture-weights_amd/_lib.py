@@ -56,6 +56,15 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'fs_plan_set_server_opt': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_float]),
+    # q-FedAvg (additive to ABI 23)
+    'fs_aggregate_qffl_ws_doubles': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_aggregate_qffl': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_qffl_coef': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    'fs_plan_set_qffl': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int64]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -350,6 +359,7 @@ KERNEL_SOURCES = {
     'aggregate_scaffold': ('aggregate_scaffold.hip', 'aggregate.hip', 'aggregate_sel.h', 'scaffold.h', 'finalize.h',
                            'common.h'),
     'aggregate_opt': ('aggregate_opt.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
+    'aggregate_qffl': ('aggregate_qffl.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'lanes.h', 'common.h'),
 }
 
 

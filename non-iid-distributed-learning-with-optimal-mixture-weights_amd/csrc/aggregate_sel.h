@@ -34,4 +34,12 @@ int aggregate_opt_launch(const float* d_W_all, int64_t stride, const int32_t* d_
                          float* d_W_g, float* d_m, float* d_v, float* d_ws, int64_t ws_floats, int chunks,
                          const EvalFinalize* fin, hipStream_t st);
 
+// fs_aggregate_qffl (aggregate_qffl.hip) with an optional finaliser, as the four above
+int aggregate_qffl_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_u,
+                          const float* d_g, double Lc, int M, int64_t len, float* d_W_g, float* d_S, double* d_n,
+                          double* d_hc, float* d_ws, int64_t ws_floats, int chunks, double* d_nws, int64_t nws_doubles,
+                          const EvalFinalize* fin, hipStream_t st);
+// the largest fs_aggregate_qffl_ws_doubles(M, len) over 1 <= M <= N
+int64_t aggregate_qffl_ws_doubles_upto(int N, int64_t len);
+
 }  // namespace fs

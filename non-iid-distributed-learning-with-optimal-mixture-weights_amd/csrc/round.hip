@@ -37,6 +37,10 @@
 // FedOpt (additive to ABI 23, fs_plan_set_server_opt): AGGREGATE launches fs_aggregate_opt
 // (aggregate_opt.hip), the mode-2 fold with a server optimizer step on its end, updating d_W_g and
 // the moments in place.  TRAIN is untouched, and the deferred evaluation's finaliser rides on it.
+//
+// q-FedAvg (additive to ABI 23, fs_plan_set_qffl): AGGREGATE launches fs_aggregate_qffl
+// (aggregate_qffl.hip), the mode-2 fold and the updates' squared norms from one pass, then the
+// q-FFL step on d_W_g in place.  TRAIN is untouched, and the finaliser rides on the pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -185,6 +189,15 @@ struct fs_plan {
   float* opt_m = nullptr;             // [C][ld] first moment
   float* opt_v = nullptr;             // [C][ld] second moment (AVGM: unused)
   float opt_eta = 0.f, opt_beta1 = 0.f, opt_omb1 = 0.f, opt_beta2 = 0.f, opt_omb2 = 0.f, opt_tau = 0.f;
+  // fs_plan_set_qffl: AGGREGATE is fs_aggregate_qffl with u = the round's weights
+  int qffl = 0;
+  const float* qf_g = nullptr;        // [N], or [M] of a subset round
+  double qf_L = 0.0;
+  float* qf_S = nullptr;              // [C][ld] the folded update
+  double* qf_n = nullptr;             // [N] / [M] squared update norms
+  double* qf_hc = nullptr;            // [2] H, coef
+  double* qf_nws = nullptr;
+  int64_t qf_nws_doubles = 0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -835,6 +848,10 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       rc = fs::aggregate_opt_launch(d.d_W_out, len, sel, pw, p->opt_rule, p->opt_eta, p->opt_beta1, p->opt_omb1,
                                     p->opt_beta2, p->opt_omb2, p->opt_tau, M, len, d.d_W_g, p->opt_m, p->opt_v,
                                     d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
+    else if (p->qffl)
+      rc = fs::aggregate_qffl_launch(d.d_W_out, len, sel, pw, p->qf_g, p->qf_L, M, len, d.d_W_g, p->qf_S, p->qf_n,
+                                     p->qf_hc, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, p->qf_nws, p->qf_nws_doubles,
+                                     f, st);
     else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
@@ -871,6 +888,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
              "mode 2 needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
   FS_REQUIRE(mode == 0 || p->opt_rule == 0,
              "a FedNova aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(mode == 0 || !p->qffl, "a FedNova aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -901,6 +919,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(!p->d.prox, "the prox term is not supported together with SCAFFOLD");
   FS_REQUIRE(p->nova_mode == 0, "SCAFFOLD and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
   FS_REQUIRE(p->opt_rule == 0, "SCAFFOLD and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "SCAFFOLD and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -931,6 +950,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
              "a server optimizer needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
   FS_REQUIRE(p->nova_mode == 0, "a server optimizer and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
   FS_REQUIRE(!p->scaffold, "a server optimizer and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(!p->qffl, "a server optimizer and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -940,6 +960,45 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   p->opt_beta2 = beta2;
   p->opt_omb2 = omb2;
   p->opt_tau = tau;
+  return FS_OK;
+}
+
+// Additive to ABI 23: q-FedAvg on the AGGREGATE phases enqueued from now on (host state, read when a
+// round call enqueues, as fs_plan_set_server_opt's).  on = 1: AGGREGATE launches fs_aggregate_qffl
+// with u = the round's weights, g = d_g, Lc, d_W_g in place, the outputs d_S / d_n / d_hc, the
+// plan's aggregation workspace and chunks, the norm workspace d_nws and the pending finaliser;
+// TRAIN is unchanged.  Lc follows the round's lr: call again before each round (allowed while on).
+// on = 0: the plain aggregate again.
+extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc, float* d_S, double* d_n, double* d_hc,
+                                double* d_nws, int64_t nws_doubles) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->qffl = 0;
+    p->qf_g = nullptr;
+    p->qf_L = 0.0;
+    p->qf_S = nullptr;
+    p->qf_n = p->qf_hc = p->qf_nws = nullptr;
+    p->qf_nws_doubles = 0;
+    return FS_OK;
+  }
+  FS_REQUIRE(d_g && d_S && d_n && d_hc && d_nws, "null pointer");
+  FS_REQUIRE(Lc > 0.0 && Lc <= 1.7976931348623157e308, "Lc must be finite and > 0");
+  FS_REQUIRE(d_S != p->d.d_W_g, "d_S and d_W_g must be different buffers");
+  FS_REQUIRE(nws_doubles >= fs::aggregate_qffl_ws_doubles_upto(p->d.N, (int64_t)p->d.C * p->d.ld),
+             "d_nws is too small (the largest fs_aggregate_qffl_ws_doubles(M, C * ld) over M <= N)");
+  FS_REQUIRE(!p->d.chained,
+             "q-FedAvg needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  FS_REQUIRE(p->nova_mode == 0, "q-FedAvg and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "q-FedAvg and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "q-FedAvg and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  p->qffl = 1;
+  p->qf_g = d_g;
+  p->qf_L = Lc;
+  p->qf_S = d_S;
+  p->qf_n = d_n;
+  p->qf_hc = d_hc;
+  p->qf_nws = d_nws;
+  p->qf_nws_doubles = nws_doubles;
   return FS_OK;
 }
 

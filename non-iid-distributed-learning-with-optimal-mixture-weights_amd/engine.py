@@ -478,6 +478,30 @@ class RoundPlan:
                    'fs_plan_set_server_opt')
         self._server_opt = (m, v)
 
+    def set_qffl(self, on, g=None, Lc=1.0, S=None, n=None, hc=None, nws=None):
+        """fs_plan_set_qffl: q-FedAvg on the AGGREGATE phases enqueued from now on -- fs_aggregate_qffl
+        with the round's weights as ``u`` (``qffl_coef``'s, passed as the round's ``p_override`` or the
+        subset round's ``q``), ``g`` ([N]; [M] of a subset round, float32), the Lipschitz estimate
+        ``Lc``, ``W_g`` in place and the outputs ``S`` [C, ld] float32, ``n`` [N] and ``hc`` [2] float64;
+        ``nws``: float64 workspace of ``fs_aggregate_qffl_ws_doubles(N, C * ld)``.  TRAIN is unchanged.
+        Device tensors the launches read and write asynchronously (the plan keeps the last ones
+        alive).  ``Lc`` follows the round's lr: call again before each round.  ``on`` false restores the
+        plain aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_qffl(self._h, 0, None, 0.0, None, None, None, None, 0), 'fs_plan_set_qffl')
+            self._qffl = None
+            return
+        for x, dt in ((g, torch.float32), (S, torch.float32), (n, torch.float64), (hc, torch.float64),
+                      (nws, torch.float64)):
+            if x is not None and not (x.is_cuda and x.dtype == dt and x.is_contiguous()):
+                raise ValueError('set_qffl: g, S (float32), n, hc and nws (float64) must be contiguous device tensors')
+        if (S is not None and S.numel() < self._desc.C * self._desc.ld) or (hc is not None and hc.numel() < 2):
+            raise ValueError('set_qffl: S needs C * ld floats, hc 2 doubles')
+        _lib.check(_lib.lib().fs_plan_set_qffl(self._h, 1, _lib.ptr(g), float(Lc), _lib.ptr(S), _lib.ptr(n),
+                                               _lib.ptr(hc), _lib.ptr(nws), 0 if nws is None else nws.numel()),
+                   'fs_plan_set_qffl')
+        self._qffl = (g, S, n, hc, nws)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -626,6 +650,67 @@ class Aggregator:
                                                _lib.ptr(m), _lib.ptr(v), _lib.ptr(self.ws), self.ws.numel(),
                                                int(self.chunks), _lib.stream_ptr()), 'fs_aggregate_opt')
         return W_g, m, v
+
+    def qffl_ws(self, M=None):
+        """A float64 workspace for ``run_qffl`` at ``M`` rows (fs_aggregate_qffl_ws_doubles); None: for
+        any M up to N, what ``RoundPlan.set_qffl`` asks for (the table is largest at the last M of a
+        regime of the fold, not always at N)."""
+        need = _lib.lib().fs_aggregate_qffl_ws_doubles
+        Ms = [int(M)] if M is not None else [self.N] + [m for m in (15, 23, 47, 95, 191, 512) if m < self.N]
+        return torch.empty(max(1, max(int(need(m, self.len)) for m in Ms)), dtype=torch.float64, device=self.ws.device)
+
+    def run_qffl(self, W_all, u, g, Lc, W_g, S, n, hc, nws, sel=None, check=True):
+        """fs_aggregate_qffl: the q-FedAvg server step from one pass over the rows ``sel`` of ``W_all``
+        (None: rows 0..len(u)-1), with x = ``W_g`` on entry: ``S = sum_k u_k*(W_k - x)`` folded as
+        ``run_opt`` folds its delta, ``n[k] = ||W_k - x||^2`` (float64) from the same loads,
+        ``H = Lc*sum(u) + sum(g*n)``, ``coef = f32(Lc / H)`` (0 when H is not finite or <= 0),
+        ``W_g += coef * S`` in place, ``hc = (H, coef)``.  ``u``, ``g``, ``W_g``, ``S`` float32; ``n`` [len(u)],
+        ``hc`` [2], ``nws`` (``qffl_ws``) float64.  ``check`` as in ``run_sel``."""
+        M = int(u.numel())
+
+        def ok(x, dt, cnt):
+            return x is not None and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= cnt
+        if not (M >= 1 and ok(u, torch.float32, M) and ok(g, torch.float32, M) and ok(W_g, torch.float32, self.len) and
+                ok(S, torch.float32, self.len) and ok(n, torch.float64, M) and ok(hc, torch.float64, 2) and
+                ok(nws, torch.float64, 1)):
+            raise ValueError('run_qffl: u, g (float32, the same non-zero length), W_g, S (float32, len), n, hc and '
+                             'nws (float64) must be contiguous device tensors')
+        if sel is not None:
+            if not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == M):
+                raise ValueError('run_qffl: sel must be a contiguous int32 device tensor as long as u')
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('run_qffl: u is longer than W_all has rows')
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_qffl: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_qffl(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                                _lib.ptr(u), _lib.ptr(g), float(Lc), M, self.len, _lib.ptr(W_g),
+                                                _lib.ptr(S), _lib.ptr(n), _lib.ptr(hc), _lib.ptr(self.ws),
+                                                self.ws.numel(), int(self.chunks), _lib.ptr(nws), nws.numel(),
+                                                _lib.stream_ptr()), 'fs_aggregate_qffl')
+        return W_g, S, n, hc
+
+
+def qffl_coef(F, p, q, L, u, g, sel=None):
+    """fs_qffl_coef: the q-FedAvg coefficients of a round on the device, from the losses
+    ``LocalEvaluator.run`` left in ``F`` [N, 2] float64: ``u_k = p_k Ft^q``, ``g_k = p_k q Ft^(q-1) L^2``
+    with ``Ft = F[sel_k, 0] + 1e-10`` (``sel`` None: row k), computed in float64 and rounded once.
+    ``p``, ``u``, ``g`` float32 device tensors of len(p) entries; ``sel`` int32 as long as ``p``."""
+    M = int(p.numel())
+    for x, dt in ((p, torch.float32), (u, torch.float32), (g, torch.float32)):
+        if not (x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= M):
+            raise ValueError('qffl_coef: p, u and g must be contiguous float32 device tensors of len(p) entries')
+    if not (F.is_cuda and F.dtype == torch.float64 and F.is_contiguous()):
+        raise ValueError('qffl_coef: F must be a contiguous float64 device tensor [N, 2]')
+    if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() >= M):
+        raise ValueError('qffl_coef: sel must be a contiguous int32 device tensor as long as p')
+    if sel is None and F.numel() < 2 * M:
+        raise ValueError('qffl_coef: F has fewer rows than p has entries')
+    _lib.check(_lib.lib().fs_qffl_coef(_lib.ptr(F), None if sel is None else _lib.ptr(sel), _lib.ptr(p), float(q),
+                                       float(L), M, _lib.ptr(u), _lib.ptr(g), _lib.stream_ptr()), 'fs_qffl_coef')
+    return u, g
 
 
 class Evaluator:

@@ -56,6 +56,8 @@ NAMES = ['CL', 'DL', 'FedAMW_OneShot', 'FedAvg', 'FedProx', 'FedAMW']
 # Scaffold (not in the reference) likewise: its row comes after FedNova's
 # the FedOpt server optimizers (not in the reference) after Scaffold's, in this order
 EXTRA = ['FedNova', 'Scaffold', 'FedAvgM', 'FedAdagrad', 'FedAdam', 'FedYogi']
+# q-FedAvg (not in the reference) after the FedOpt rows; a list of its own, so that EXTRA keeps its value
+EXTRA_FAIR = ['QFedAvg']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -93,15 +95,17 @@ def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None
 def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batch_size=32, n_repeats=1,
         alpha_Dirk=0.01, data_dir='../FedAMW/datasets/', result_dir='./results', save=True, clients='sequential',
         algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None, participation=None,
-        sample_seed=0, server_lr=None, server_beta1=0.9, server_beta2=0.99, server_tau=1e-3):
+        sample_seed=0, server_lr=None, server_beta1=0.9, server_beta2=0.99, server_tau=1e-3, qffl_q=1.0,
+        qffl_weighting='size'):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
         raise ValueError("local_eval must be None, 'global', 'own' or 'both'")
-    unknown = [n for n in algos if n not in NAMES + EXTRA]
+    known = NAMES + EXTRA + EXTRA_FAIR
+    unknown = [n for n in algos if n not in known]
     if unknown:
-        raise ValueError('unknown algorithm(s) %s (known: %s)' % (', '.join(unknown), ', '.join(NAMES + EXTRA)))
-    names = list(NAMES) + [n for n in EXTRA if n in algos]
+        raise ValueError('unknown algorithm(s) %s (known: %s)' % (', '.join(unknown), ', '.join(known)))
+    names = list(NAMES) + [n for n in EXTRA + EXTRA_FAIR if n in algos]
     lwant = {None: (), 'both': ('global', 'own')}.get(local_eval, (local_eval,))
     want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
     cev = {'client_%s_%s' % (w, m): [None] * len(names) for w in want for m in ('loss', 'acc')}
@@ -238,6 +242,18 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             keep_participants(name, st)
             k = names.index(name)
             train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        if 'QFedAvg' in algos:
+            # FedAvg's arguments; clients are always parallel
+            st = ce('QFedAvg', False)
+            if participation is not None:
+                st = st or {}
+            qpar = dict(kw) if participation is None else dict(participation=participation, sample_seed=sample_seed,
+                                                               **kw)
+            r = timed('QFedAvg', lambda: tools.QFedAvg(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False, 0,
+                                                       Round, q=qffl_q, weighting=qffl_weighting, stats=st, **qpar))
+            keep_participants('QFedAvg', st)
+            k = names.index('QFedAvg')
+            train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -271,7 +287,7 @@ def main(argv=None):
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES),
                     help='comma-separated; FedNova (exp.py:124, commented out there), Scaffold, FedAvgM, FedAdagrad, '
-                         'FedAdam and FedYogi run only when named here')
+                         'FedAdam, FedYogi and QFedAvg run only when named here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -279,8 +295,8 @@ def main(argv=None):
                     help="score the round's global model / every client's own model on each client's own rows")
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
-                         'Applies to the FedAvg, FedProx, FedNova, Scaffold and server-optimizer (FedAvgM, FedAdagrad, '
-                         'FedAdam, FedYogi) calls only, which then run with parallel clients '
+                         'Applies to the FedAvg, FedProx, FedNova, Scaffold, server-optimizer (FedAvgM, FedAdagrad, '
+                         'FedAdam, FedYogi) and QFedAvg calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')
@@ -289,12 +305,15 @@ def main(argv=None):
     ap.add_argument('--server-beta1', type=float, default=0.9, help='server momentum / first-moment decay')
     ap.add_argument('--server-beta2', type=float, default=0.99, help='second-moment decay (FedAdam, FedYogi)')
     ap.add_argument('--server-tau', type=float, default=1e-3, help='adaptivity of the adaptive server optimizers')
+    ap.add_argument('--qffl-q', type=float, default=1.0, help='QFedAvg: the fairness exponent q >= 0 (0: FedAvg)')
+    ap.add_argument('--qffl-weighting', default='size', choices=['size', 'uniform'],
+                    help='QFedAvg: the client weights p_k, n_k / n or 1 / N')
     a = ap.parse_args(argv)
     out = run(a.dataset, a.D, a.clients, a.local_epoch, a.rounds, a.batch_size, a.repeats, a.alpha, a.data_dir,
               a.result_dir, True, a.mode, tuple(a.algos.split(',')), verbose=not a.quiet, client_eval=a.client_eval,
               local_eval=a.local_eval, participation=a.participation, sample_seed=a.sample_seed,
               server_lr=a.server_lr, server_beta1=a.server_beta1, server_beta2=a.server_beta2,
-              server_tau=a.server_tau)
+              server_tau=a.server_tau, qffl_q=a.qffl_q, qffl_weighting=a.qffl_weighting)
     for k, name in enumerate(out['name']):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

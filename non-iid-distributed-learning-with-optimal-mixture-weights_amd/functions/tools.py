@@ -390,6 +390,27 @@ def server_opt_scalars(server_opt, server_lr=None, beta1=0.9, beta2=0.99, tau=1e
             f(1.0 - float(beta2)), f(float(tau)))
 
 
+def _check_qffl(q, weighting, lipschitz, clients='parallel'):
+    """QFedAvg's keyword checks (host only: before any device is touched)."""
+    if not float(q) >= 0.0 or float(q) == float('inf'):
+        raise ValueError('q must be finite and >= 0')
+    if weighting not in SCAFFOLD_WEIGHTINGS:
+        raise ValueError("weighting must be 'size' or 'uniform'")
+    if lipschitz is not None and not (0.0 < float(lipschitz) < float('inf')):
+        raise ValueError('lipschitz must be finite and > 0')
+    if clients != 'parallel':
+        raise ValueError("QFedAvg needs clients='parallel': a chained client's W_j - W_g contains its predecessors' "
+                         "work")
+
+
+def qffl_lipschitz(lr, R, lipschitz=None):
+    """q-FedAvg's Lipschitz estimate of every round (float64): ``lipschitz`` where given, else
+    1 / lr_t with the round's decayed learning rate (``scaffold_lr_schedule``)."""
+    if lipschitz is not None:
+        return [float(lipschitz)] * int(R)
+    return [1.0 / float(v) for v in scaffold_lr_schedule(lr, R)]
+
+
 class Federation:
     """One algorithm call split into setup / rounds / results (bench.py drives the
     rounds one at a time through the same code path as the drop-ins)."""
@@ -397,7 +418,13 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size', server_opt=None):
+                 server_lr=1.0, weighting='size', server_opt=None, qffl=None):
+        self.qffl = algo == 'qfedavg'
+        if self.qffl:
+            # qffl: dict(q=, lipschitz=) (tools.QFedAvg); weighting is the keyword above
+            qf = dict(qffl or {})
+            self.qf_q, self.qf_lipschitz = float(qf.get('q', 1.0)), qf.get('lipschitz')
+            _check_qffl(self.qf_q, weighting, self.qf_lipschitz, clients)
         self.fedopt = algo == 'fedopt'
         if self.fedopt:
             # server_opt: dict(rule=, server_lr=, beta1=, beta2=, tau=, v0=) (tools.FedOpt)
@@ -440,9 +467,9 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt'):
-                raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold and '
-                                          'FedOpt only')
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg'):
+                raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
+                                          'FedOpt and QFedAvg only')
             if self.chained:
                 raise ValueError("participation needs clients='parallel': every sampled client starts from the "
                                  "round's global model (clients='sequential' chains all clients)")
@@ -456,6 +483,9 @@ class Federation:
         if self.fedopt and nranks > 1:
             # (delta would need its all-reduce before the nonlinear step)
             raise NotImplementedError('FedOpt over more than one torch.distributed rank is not implemented')
+        if self.qffl and nranks > 1:
+            # (S, the norms and H would need their all-reduce before the step)
+            raise NotImplementedError('QFedAvg over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -639,6 +669,26 @@ class Federation:
             trace = stats is not None and stats.get('trace')
             self.m_hist = torch.empty(R, C, ld, device=dev) if trace else None
             self.v_hist = torch.empty(R, C, ld, device=dev) if trace else None
+        if self.qffl:
+            # q-FedAvg: FedAvg's round with fs_aggregate_qffl as its aggregate, after one local
+            # evaluation of the round's starting model and fs_qffl_coef.  p_k over ALL N clients
+            # (H normalises), per round the sampled ones' in ascending id; L_t on the host
+            p64 = scaffold_weights(ns, weighting)
+            Mx = N if self.sched is None else self.sel_dev.shape[1]
+            p_h = np.zeros((R, Mx), np.float32)
+            for t in range(R):
+                S = np.arange(N) if self.sched is None else self.sched[t]
+                p_h[t, :len(S)] = p64[S].astype(np.float32)
+            self.qf_p_dev = torch.from_numpy(p_h).to(dev)
+            self.qf_L = qffl_lipschitz(lr, R, self.qf_lipschitz)
+            self.qf_eval = self.local_eval or engine.LocalEvaluator(self.feats, C, loss=loss)
+            self.qf_F = torch.zeros(R, N, 2, dtype=torch.float64, device=dev)
+            self.qf_u = torch.zeros(Mx, dtype=torch.float32, device=dev)
+            self.qf_g = torch.zeros(Mx, dtype=torch.float32, device=dev)
+            self.qf_S = torch.zeros(C, ld, dtype=torch.float32, device=dev)
+            self.qf_n = torch.full((R, Mx), float('nan'), dtype=torch.float64, device=dev)
+            self.qf_hc = torch.zeros(R, 2, dtype=torch.float64, device=dev)
+            self.qf_nws = self.agg.qffl_ws()
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -707,6 +757,15 @@ class Federation:
 
         if self.scaffold:
             self.plan.set_scaffold(True, self.c_var, self.ci_var, self.sc_r_dev[t], self.sc_cs[t])
+        if self.qffl:
+            # F_k(W_g) on every client's own rows (all N, also under participation: fs_eval_clients
+            # has no subset form), then u and g of the sampled ones, all on the device
+            M_t = self.N if self.sched is None else len(self.sched[t])
+            timed('qffl_eval', lambda: self.qf_eval.run(self.W_g, 0, self.qf_F[t]))
+            timed('qffl_coef', lambda: engine.qffl_coef(self.qf_F[t], self.qf_p_dev[t][:M_t], self.qf_q, self.qf_L[t],
+                                                        self.qf_u, self.qf_g,
+                                                        None if self.sched is None else self.sel_dev[t][:M_t]))
+            self.plan.set_qffl(True, self.qf_g, self.qf_L[t], self.qf_S, self.qf_n[t], self.qf_hc[t], self.qf_nws)
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -715,10 +774,12 @@ class Federation:
                                    *self.nova_round[t])
 
             def plan_round(phases):
-                self.plan.round_subset(t, self.lr, phases, self.sel_dev[t], self.sel_order_dev[t], self.q_dev[t], M)
+                self.plan.round_subset(t, self.lr, phases, self.sel_dev[t], self.sel_order_dev[t],
+                                       self.qf_u if self.qffl else self.q_dev[t], M)
         else:
             def plan_round(phases):
-                self.plan.round(t, self.lr, phases, self.sc_q_dev[t] if self.scaffold else None)
+                self.plan.round(t, self.lr, phases,
+                                self.sc_q_dev[t] if self.scaffold else self.qf_u if self.qffl else None)
         timed('train', lambda: plan_round(P[0]))
         # (under participation the two evaluations of the clients' OWN models below still score all
         # N rows of W_out -- stale rows of clients that sat the round out, zeros before a client's
@@ -853,6 +914,15 @@ class Federation:
                 if self.m_hist is not None:
                     self.stats['server_m_rounds'] = self.m_hist[:R, :, :D].cpu().numpy()
                     self.stats['server_v_rounds'] = self.v_hist[:R, :, :D].cpu().numpy()
+            if self.qffl:
+                self.stats['client_loss'] = self.qf_F[:R, :, 0].cpu().numpy()
+                nh = self.qf_n[:R].cpu().numpy()
+                norms = np.full((R, self.N), np.nan)
+                for t in range(R):
+                    S = np.arange(self.N) if self.sched is None else self.sched[t]
+                    norms[t, S] = nh[t, :len(S)]
+                self.stats['update_norms'] = norms
+                self.stats['qffl_coef'] = self.qf_hc[:R].cpu().numpy()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -995,6 +1065,36 @@ def _adaptive(rule):
 
 
 FedAdagrad, FedAdam, FedYogi = _adaptive('adagrad'), _adaptive('adam'), _adaptive('yogi')
+
+
+def QFedAvg(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, q=1.0,
+            weighting='size', lipschitz=None, stats=None, verbose=True, options=None, participation=None,
+            sample_seed=0):
+    """q-FedAvg (q-FFL; Li, Sanjabi, Beirami, Smith, ICLR 2020; not in the reference): FedAvg's positional
+    list, clients always parallel.  Local training is FedAvg's launch unchanged -- both tasks,
+    ``prox=True``, any ``batch_size`` the task's trainer accepts, ``participation`` -- and only the server
+    step differs.  With x the round's starting model, F_k its loss on client k's own rows (mean
+    cross-entropy or MSE, ``LocalEvaluator``), Ft = F_k + 1e-10, L the Lipschitz estimate
+    (``lipschitz``; None: 1 / lr_t with the round's decayed learning rate) and S the sampled clients:
+    u_k = p_k Ft^q,  g_k = p_k q Ft^(q-1) L^2  (fs_qffl_coef);
+    x' = x + (L / H) sum_S u_k (W_k - x),  H = L sum_S u_k + sum_S g_k ||W_k - x||^2  (fs_aggregate_qffl,
+    the fold and the norms from one pass) -- the paper's w - sum Delta_k / sum h_k.
+    ``weighting='size'``: p_k = n_k / n; ``'uniform'``: p_k = 1 / N; over all N clients, not renormalised
+    over the sample (H normalises), so ``q=0`` is FedAvg over the sample.  A round enqueues, on one
+    stream: the local evaluation of x, fs_qffl_coef, FedAvg's TRAIN, AGGREGATE and EVAL.  Under
+    ``participation`` the evaluation still scores all N clients (fs_eval_clients has no subset form)
+    and the sample is uniform as FedAvg's (not the paper's sampling by p_k).  The global generator
+    is consumed exactly as by ``FedAvg(clients='parallel')`` with the same ``participation``, and
+    ``train_loss`` is FedAvg's.  ``stats['client_loss']`` [R, N] float64 (the F_k of each round's
+    starting model), ``stats['update_norms']`` [R, N] (||W_k - x||^2, NaN where a client was not sampled),
+    ``stats['qffl_coef']`` [R, 2] (H and coef = f32(L / H)).  ValueError for ``q < 0``, ``lipschitz <= 0``
+    and an unknown ``weighting``; NotImplementedError over more than one torch.distributed rank."""
+    _check_qffl(q, weighting, lipschitz)
+    return _run('qfedavg', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed, weighting=weighting,
+                qffl=dict(q=q, lipschitz=lipschitz))
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
