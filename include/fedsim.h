@@ -477,6 +477,47 @@ int fs_qffl_coef(const double* d_F2, const int32_t* d_sel, const float* d_p, dou
                  float* d_g, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Robust aggregation: the coordinate-wise beta-trimmed mean and median (Yin, Chen, Ramchandran,
+ * Bartlett, ICML 2018).  Additive to ABI 23: three new entry points, FS_ABI_VERSION unchanged.
+ *
+ * fs_aggregate_robust: over the M rows d_sel (NULL: rows 0..M-1) of d_W_all, each of len floats,
+ * with the trim count b, 0 <= 2b < M, for every coordinate i on its own:
+ *   Order.  The M values are ordered by the monotone 32-bit key of a float's bits,
+ *     key = bits ^ 0xFFFFFFFF when the sign bit is set, bits | 0x80000000 otherwise:
+ *     a total order with -0 < +0, +Inf and sign-clear NaNs at the top, -Inf and sign-set NaNs at
+ *     the bottom.
+ *   Kept.   The ranks b+1 .. M-b of that order (n = M - 2b values, a multiset).  Values that tie
+ *     at a threshold have equal keys, hence equal bits: which of them are kept cannot matter.
+ *   Output. d_out[i] = (float)(S / (double)n), S the sum of the kept values as doubles.
+ *   b = 0 is the uniform mean, b = (M-1)/2 the median (odd M: the middle value itself, even M:
+ *   the mean of the two middle values).  Up to b rows of arbitrary bits per side are discarded
+ *   per coordinate (Inf and NaN included); a NaN that survives the trim makes that coordinate
+ *   NaN (with whatever payload: callers compare NaN as NaN).
+ *   Summation order of S (IEEE double, no fused multiply-add), with lo and hi the values at ranks
+ *   b+1 and M-b, clo and chi the number of kept copies of each (lo == hi as keys: clo = n,
+ *   chi = 0), T = 256 / width slices and width = 32 columns for M <= 1261, 16 for M <= 2523,
+ *   8 above:
+ *     n <= 2:  S = clo * lo, then + chi * hi when chi > 0;
+ *     else     slice s (0 <= s < T) = 0.0 + the values strictly between lo and hi (by key) at
+ *              k = s, s + T, s + 2T, ... in ascending k (k the position in d_sel);
+ *              the slices joined by the pairwise tree p[j] += p[j + h] for j = 0, 2h, 4h, ...,
+ *              h = 1, 2, 4, ... < T;   S = (tree + clo * lo), then + chi * hi when chi > 0.
+ *   tests/robust_restatement.py restates this in numpy; the kernel equals it bit for bit, and it
+ *   is within 2^-24 |ref| + n 2^-52 mean|kept| + 2^-149 of the sorted float64 mean ref.
+ * Every selected row element is loaded once, rows outside d_sel are never read, d_W_all is the
+ * only input: d_out may be any buffer that is not part of the selected rows (the global model).
+ * One launch; no global atomics, no cross-workgroup wait, no allocation, no host synchronisation;
+ * the same bits on every call and for the same rows gathered from a larger buffer.
+ * FS_EINVAL for M < 1, M > fs_aggregate_robust_max_m(), 2b >= M or b < 0, len or stride no
+ * multiple of 4, stride < len or a null pointer (d_sel may be NULL); nothing is launched then.
+ * fs_aggregate_robust_max_m: the largest M the kernel accepts (5047: the M rows of a stripe of 8
+ * columns in one CU's LDS).
+ * ------------------------------------------------------------------------- */
+int fs_aggregate_robust(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len, int b,
+                        float* d_out, void* stream);
+int fs_aggregate_robust_max_m(void);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -918,6 +959,21 @@ int fs_plan_set_server_opt(fs_plan* plan, int rule, float* d_m, float* d_v, floa
  * fs_plan_set_server_opt refuse in turn while it is on. */
 int fs_plan_set_qffl(fs_plan* plan, int on, const float* d_g, double Lc, float* d_S, double* d_n, double* d_hc,
                      double* d_nws, int64_t nws_doubles);
+
+/* (additive to ABI 23) robust aggregation on this plan's AGGREGATE phase.  Host state read when the
+ * next round call enqueues, as fs_plan_set_server_opt's.  on = 1: AGGREGATE launches
+ * fs_aggregate_robust over the round's rows of d_W_out (all N, or the subset call's M ids) into
+ * d_W_g, with the pending finaliser of a deferred evaluation.  mode FS_ROBUST_TRIMMED_MEAN (1):
+ * b = floor(trim * M) in double, M the round's own client count, clamped to (M-1)/2;
+ * mode FS_ROBUST_MEDIAN (2): b = (M-1)/2 (trim is ignored).  The rule is unweighted: the round's
+ * weights are not read.  TRAIN and EVAL are unchanged: every training form, the prox term, loss = 1,
+ * B > 64 and subset rounds work as without it.  on = 0 restores the plain aggregate.  FS_EINVAL for
+ * a chained plan, N > fs_aggregate_robust_max_m(), an unknown mode, trim outside [0, 0.5), a nova
+ * mode other than 0, SCAFFOLD on, a server-optimizer rule set or q-FedAvg on; fs_plan_set_nova,
+ * fs_plan_set_scaffold, fs_plan_set_server_opt and fs_plan_set_qffl refuse in turn while it is on. */
+#define FS_ROBUST_TRIMMED_MEAN 1
+#define FS_ROBUST_MEDIAN 2
+int fs_plan_set_robust(fs_plan* plan, int on, int mode, double trim);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

@@ -65,6 +65,11 @@ _SIGS = {
                                C.c_void_p, C.c_void_p]),
     'fs_plan_set_qffl': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int64]),
+    # robust aggregation (additive to ABI 23)
+    'fs_aggregate_robust': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
+    'fs_aggregate_robust_max_m': (C.c_int, []),
+    'fs_plan_set_robust': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -129,6 +134,7 @@ ABI_VERSION = 23
 PHASE_TRAIN, PHASE_AGGREGATE, PHASE_EVAL, PHASE_EVAL_DEFER = 1, 2, 4, 8
 NOVA_REFERENCE, NOVA_UPDATES = 1, 2   # fs_aggregate_nova / fs_plan_set_nova modes (ABI 23)
 OPT_AVGM, OPT_ADAGRAD, OPT_ADAM, OPT_YOGI = 1, 2, 3, 4   # fs_aggregate_opt / fs_plan_set_server_opt rules
+ROBUST_TRIMMED_MEAN, ROBUST_MEDIAN = 1, 2   # fs_plan_set_robust modes
 OPT_RULES = {'avgm': OPT_AVGM, 'adagrad': OPT_ADAGRAD, 'adam': OPT_ADAM, 'yogi': OPT_YOGI}
 G_PAIR = 256            # fs_local_train_plan: G | G_PAIR = the pair-client form at width G (ABI 10)
 G_TEAMS = 512            # fs_local_train_plan: G | G_TEAMS = the team form at width G (ABI 13)
@@ -360,6 +366,7 @@ KERNEL_SOURCES = {
                            'common.h'),
     'aggregate_opt': ('aggregate_opt.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_qffl': ('aggregate_qffl.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'lanes.h', 'common.h'),
+    'aggregate_robust': ('aggregate_robust.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
 }
 
 

@@ -42,4 +42,9 @@ int aggregate_qffl_launch(const float* d_W_all, int64_t stride, const int32_t* d
 // the largest fs_aggregate_qffl_ws_doubles(M, len) over 1 <= M <= N
 int64_t aggregate_qffl_ws_doubles_upto(int N, int64_t len);
 
+// fs_aggregate_robust (aggregate_robust.hip) with an optional finaliser, as the five above (one launch
+// at every M: the finaliser always rides)
+int aggregate_robust_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len, int b,
+                            float* d_out, const EvalFinalize* fin, hipStream_t st);
+
 }  // namespace fs

@@ -41,6 +41,10 @@
 // q-FedAvg (additive to ABI 23, fs_plan_set_qffl): AGGREGATE launches fs_aggregate_qffl
 // (aggregate_qffl.hip), the mode-2 fold and the updates' squared norms from one pass, then the
 // q-FFL step on d_W_g in place.  TRAIN is untouched, and the finaliser rides on the pass.
+//
+// Robust aggregation (additive to ABI 23, fs_plan_set_robust): AGGREGATE launches fs_aggregate_robust
+// (aggregate_robust.hip), the coordinate-wise trimmed mean or median of the round's rows into
+// d_W_g; the round's weights are not read.  TRAIN is untouched, and the finaliser rides on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,6 +58,7 @@
 #include <vector>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 
 #include "aggregate_sel.h"
@@ -198,6 +203,9 @@ struct fs_plan {
   double* qf_hc = nullptr;            // [2] H, coef
   double* qf_nws = nullptr;
   int64_t qf_nws_doubles = 0;
+  // fs_plan_set_robust: AGGREGATE is fs_aggregate_robust (0 off, FS_ROBUST_*)
+  int robust = 0;
+  double rb_trim = 0.0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -852,7 +860,11 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       rc = fs::aggregate_qffl_launch(d.d_W_out, len, sel, pw, p->qf_g, p->qf_L, M, len, d.d_W_g, p->qf_S, p->qf_n,
                                      p->qf_hc, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, p->qf_nws, p->qf_nws_doubles,
                                      f, st);
-    else if (p->nova_mode)
+    else if (p->robust) {
+      // b from the round's own client count, so that 2b < M
+      const int b = p->robust == FS_ROBUST_MEDIAN ? (M - 1) / 2 : std::min((int)std::floor(p->rb_trim * (double)M), (M - 1) / 2);
+      rc = fs::aggregate_robust_launch(d.d_W_out, len, sel, M, len, b, d.d_W_g, f, st);
+    } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
     else if (sub)
@@ -889,6 +901,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   FS_REQUIRE(mode == 0 || p->opt_rule == 0,
              "a FedNova aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(mode == 0 || !p->qffl, "a FedNova aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(mode == 0 || !p->robust, "a FedNova aggregate and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -920,6 +933,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(p->nova_mode == 0, "SCAFFOLD and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
   FS_REQUIRE(p->opt_rule == 0, "SCAFFOLD and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->qffl, "SCAFFOLD and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "SCAFFOLD and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -951,6 +965,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   FS_REQUIRE(p->nova_mode == 0, "a server optimizer and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
   FS_REQUIRE(!p->scaffold, "a server optimizer and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
   FS_REQUIRE(!p->qffl, "a server optimizer and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "a server optimizer and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -991,6 +1006,7 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   FS_REQUIRE(p->nova_mode == 0, "q-FedAvg and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
   FS_REQUIRE(!p->scaffold, "q-FedAvg and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
   FS_REQUIRE(p->opt_rule == 0, "q-FedAvg and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->robust, "q-FedAvg and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   p->qffl = 1;
   p->qf_g = d_g;
   p->qf_L = Lc;
@@ -999,6 +1015,33 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   p->qf_hc = d_hc;
   p->qf_nws = d_nws;
   p->qf_nws_doubles = nws_doubles;
+  return FS_OK;
+}
+
+// Additive to ABI 23: robust aggregation on the AGGREGATE phases enqueued from now on (host state,
+// read when a round call enqueues).  on = 1: AGGREGATE launches fs_aggregate_robust over the round's
+// rows into d_W_g with b from `mode`, `trim` and the round's own client count; the weights are
+// ignored, TRAIN is unchanged.  on = 0: the plain aggregate again.
+extern "C" int fs_plan_set_robust(fs_plan* p, int on, int mode, double trim) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->robust = 0;
+    p->rb_trim = 0.0;
+    return FS_OK;
+  }
+  FS_REQUIRE(mode == FS_ROBUST_TRIMMED_MEAN || mode == FS_ROBUST_MEDIAN,
+             "mode must be FS_ROBUST_TRIMMED_MEAN or FS_ROBUST_MEDIAN");
+  FS_REQUIRE(mode == FS_ROBUST_MEDIAN || (trim >= 0.0 && trim < 0.5), "trim must be in [0, 0.5)");
+  FS_REQUIRE(!p->d.chained,
+             "a robust aggregate needs parallel clients (a chained client's row holds its predecessors' work)");
+  FS_REQUIRE(p->d.N <= fs_aggregate_robust_max_m(), "N is larger than fs_aggregate_robust_max_m()");
+  FS_REQUIRE(p->nova_mode == 0, "a robust aggregate and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "a robust aggregate and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0,
+             "a robust aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "a robust aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  p->robust = mode;
+  p->rb_trim = mode == FS_ROBUST_MEDIAN ? 0.0 : trim;
   return FS_OK;
 }
 

@@ -502,6 +502,20 @@ class RoundPlan:
                    'fs_plan_set_qffl')
         self._qffl = (g, S, n, hc, nws)
 
+    def set_robust(self, on, mode='trimmed_mean', trim=0.1):
+        """fs_plan_set_robust: robust aggregation on the AGGREGATE phases enqueued from now on --
+        fs_aggregate_robust over the round's rows of ``W_out`` into ``W_g``.  ``mode='trimmed_mean'``:
+        b = floor(trim * M) with M the round's own client count (N, or a subset round's M), clamped
+        so that 2b < M; ``mode='median'``: b = (M - 1) // 2.  The rule is unweighted: the round's
+        weights are ignored.  TRAIN and EVAL are unchanged.  ``on`` false restores the plain aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_robust(self._h, 0, 0, 0.0), 'fs_plan_set_robust')
+            return
+        modes = {'trimmed_mean': _lib.ROBUST_TRIMMED_MEAN, 'median': _lib.ROBUST_MEDIAN}
+        if mode not in modes:
+            raise ValueError("set_robust: mode must be 'trimmed_mean' or 'median'")
+        _lib.check(_lib.lib().fs_plan_set_robust(self._h, 1, modes[mode], float(trim)), 'fs_plan_set_robust')
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -691,6 +705,39 @@ class Aggregator:
                                                 self.ws.numel(), int(self.chunks), _lib.ptr(nws), nws.numel(),
                                                 _lib.stream_ptr()), 'fs_aggregate_qffl')
         return W_g, S, n, hc
+
+    def run_robust(self, W_all, b, out, sel=None, check=True):
+        """fs_aggregate_robust: the coordinate-wise trimmed mean of the rows ``sel`` of ``W_all`` (None:
+        rows 0..N-1) with the trim count ``b``, 0 <= 2b < M: per coordinate the b smallest and the b
+        largest values (by the total order of include/fedsim.h: -0 < +0, NaN at the ends) are
+        dropped and the rest averaged in float64, rounded once.  ``b = 0``: the uniform mean;
+        ``b = (M - 1) // 2``: the median.  ``out`` float32 [len], any buffer outside the selected rows.
+        One launch; ``check`` as in ``run_sel``.  ValueError for M above ``robust_max_m()``."""
+        M = self.N if sel is None else int(sel.numel())
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= self.len
+                and W_all.is_cuda and W_all.dtype == torch.float32 and W_all.is_contiguous()):
+            raise ValueError('run_robust: W_all and out must be contiguous float32 device tensors')
+        if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and M >= 1):
+            raise ValueError('run_robust: sel must be a contiguous, non-empty int32 device tensor')
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('run_robust: W_all has fewer than N rows')
+        if M > robust_max_m():
+            raise ValueError('run_robust: M = %d is above fs_aggregate_robust_max_m() = %d' % (M, robust_max_m()))
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('run_robust: sel must index rows of W_all, [0, %d)' % rows)
+        _lib.check(_lib.lib().fs_aggregate_robust(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                                  self.len, int(b), _lib.ptr(out), _lib.stream_ptr()),
+                   'fs_aggregate_robust')
+        return out
+
+
+def robust_max_m():
+    """fs_aggregate_robust_max_m: the largest number of rows ``Aggregator.run_robust`` accepts."""
+    return int(_lib.lib().fs_aggregate_robust_max_m())
+
 
 
 def qffl_coef(F, p, q, L, u, g, sel=None):

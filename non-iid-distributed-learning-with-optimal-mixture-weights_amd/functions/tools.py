@@ -86,6 +86,8 @@ or non-finite targets; ``num_classes != 1`` raises NotImplementedError, any othe
 ValueError.  ``stats['W_global']`` is [1, D] and ``stats['W_rounds']`` [R, 1, D].
 """
 
+import math
+
 import numpy as np
 import torch
 
@@ -411,6 +413,78 @@ def qffl_lipschitz(lr, R, lipschitz=None):
     return [1.0 / float(v) for v in scaffold_lr_schedule(lr, R)]
 
 
+ROBUST_RULES = ('median', 'trimmed_mean', 'mean')
+BYZANTINE_ATTACKS = ('sign_flip', 'gaussian', 'nan')
+
+
+def _check_robust(rule, trim, clients='parallel'):
+    """FedRobust's keyword checks (host only: before any device is touched)."""
+    if rule not in ROBUST_RULES:
+        raise ValueError("rule must be 'median', 'trimmed_mean' or 'mean'")
+    if not (0.0 <= float(trim) < 0.5):
+        raise ValueError('trim must be in [0, 0.5)')
+    if clients != 'parallel':
+        raise ValueError("FedRobust needs clients='parallel': a chained client's row holds its predecessors' work")
+
+
+def robust_trim_count(rule, trim, M):
+    """The trim count b of a round of M clients, as fs_plan_set_robust takes it: 'median' (M - 1) // 2,
+    'trimmed_mean' floor(trim * M) in float64 clamped so that 2b < M, 'mean' 0."""
+    M = int(M)
+    if rule == 'median':
+        return (M - 1) // 2
+    if rule == 'mean':
+        return 0
+    return min(int(math.floor(float(trim) * float(M))), (M - 1) // 2)
+
+
+def _check_robust_rounds(Ms, max_m):
+    """ValueError for a round that no client trains in or whose client count exceeds ``max_m``."""
+    for t, M in enumerate(Ms):
+        if M < 1:
+            raise ValueError('FedRobust: round %d samples no client' % t)
+        if M > max_m:
+            raise ValueError('FedRobust: round %d has M = %d clients, above fs_aggregate_robust_max_m() = %d'
+                             % (t, M, max_m))
+
+
+def byzantine_plan(N, byzantine):
+    """``byzantine=`` checked and resolved (host only): None, or (sorted int64 ids, attack, scale, seed).
+    ``ids``: the client ids given; ``fraction``: floor(fraction * N) ids fixed once from ``seed``
+    (the first of a ``torch.randperm(N)`` of a private generator)."""
+    if byzantine is None:
+        return None
+    bz = dict(byzantine)
+    unknown = set(bz) - {'ids', 'fraction', 'attack', 'scale', 'seed'}
+    if unknown:
+        raise ValueError('unknown byzantine key(s) %s' % ', '.join(sorted(unknown)))
+    if ('ids' in bz) == ('fraction' in bz):
+        raise ValueError("byzantine needs exactly one of 'ids' and 'fraction'")
+    attack, scale, seed = bz.get('attack', 'sign_flip'), float(bz.get('scale', 1.0)), int(bz.get('seed', 0))
+    if attack not in BYZANTINE_ATTACKS:
+        raise ValueError("byzantine attack must be 'sign_flip', 'gaussian' or 'nan'")
+    if 'ids' in bz:
+        ids = np.unique(np.asarray(list(bz['ids']), dtype=np.int64))
+        if len(ids) and (ids[0] < 0 or ids[-1] >= N):
+            raise ValueError('byzantine ids must be client ids in [0, %d)' % N)
+    else:
+        f = float(bz['fraction'])
+        if not (0.0 <= f <= 1.0):
+            raise ValueError('byzantine fraction must be in [0, 1]')
+        g = torch.Generator()
+        g.manual_seed(seed)
+        ids = np.sort(torch.randperm(int(N), generator=g)[:int(math.floor(f * N))].numpy().astype(np.int64))
+    return ids, attack, scale, seed
+
+
+def byzantine_noise(seed, t, shape):
+    """The N(0, 1) draws of ``attack='gaussian'`` for round ``t``: a private CPU generator seeded by
+    (seed, t), float32 of ``shape`` (rows in ascending client id)."""
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 1000003 + int(t)) % (1 << 62))
+    return torch.randn(*shape, generator=g, dtype=torch.float32)
+
+
 class Federation:
     """One algorithm call split into setup / rounds / results (bench.py drives the
     rounds one at a time through the same code path as the drop-ins)."""
@@ -418,7 +492,15 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size', server_opt=None, qffl=None):
+                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None):
+        self.robust = algo == 'fedrobust'
+        self.byz = None
+        if self.robust:
+            # robust: dict(rule=, trim=, byzantine=) (tools.FedRobust)
+            rb = dict(robust or {})
+            self.rb_rule, self.rb_trim = rb.get('rule', 'median'), float(rb.get('trim', 0.1))
+            _check_robust(self.rb_rule, self.rb_trim, clients)
+            self.byz = byzantine_plan(len(y_train), rb.get('byzantine'))
         self.qffl = algo == 'qfedavg'
         if self.qffl:
             # qffl: dict(q=, lipschitz=) (tools.QFedAvg); weighting is the keyword above
@@ -467,9 +549,9 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg'):
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust'):
                 raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
-                                          'FedOpt and QFedAvg only')
+                                          'FedOpt, QFedAvg and FedRobust only')
             if self.chained:
                 raise ValueError("participation needs clients='parallel': every sampled client starts from the "
                                  "round's global model (clients='sequential' chains all clients)")
@@ -486,6 +568,13 @@ class Federation:
         if self.qffl and nranks > 1:
             # (S, the norms and H would need their all-reduce before the step)
             raise NotImplementedError('QFedAvg over more than one torch.distributed rank is not implemented')
+        if self.robust:
+            if nranks > 1:
+                # (an order statistic over all clients' rows is no sum of the ranks' parts)
+                raise NotImplementedError('FedRobust over more than one torch.distributed rank is not implemented')
+            self.rb_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
+            _check_robust_rounds(self.rb_M, engine.robust_max_m())
+            self.rb_b = [robust_trim_count(self.rb_rule, self.rb_trim, M) for M in self.rb_M]
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -689,6 +778,11 @@ class Federation:
             self.qf_n = torch.full((R, Mx), float('nan'), dtype=torch.float64, device=dev)
             self.qf_hc = torch.zeros(R, 2, dtype=torch.float64, device=dev)
             self.qf_nws = self.agg.qffl_ws()
+        if self.robust:
+            # FedAvg's round with fs_aggregate_robust as its aggregate; b follows each round's own
+            # client count inside the plan ('mean': trim 0)
+            self.plan.set_robust(True, 'median' if self.rb_rule == 'median' else 'trimmed_mean',
+                                 self.rb_trim if self.rb_rule == 'trimmed_mean' else 0.0)
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -781,6 +875,8 @@ class Federation:
                 self.plan.round(t, self.lr, phases,
                                 self.sc_q_dev[t] if self.scaffold else self.qf_u if self.qffl else None)
         timed('train', lambda: plan_round(P[0]))
+        if self.byz is not None:
+            timed('byzantine', lambda: self._corrupt(t))
         # (under participation the two evaluations of the clients' OWN models below still score all
         # N rows of W_out -- stale rows of clients that sat the round out, zeros before a client's
         # first round -- and results() masks the unsampled ones to NaN: both evaluators walk the
@@ -859,6 +955,23 @@ class Federation:
         elif self.t < self.R and not early:
             self._prepare_upto(self.t + 1)
 
+    def _corrupt(self, t):
+        """``byzantine=``: overwrite the corrupted clients' rows of ``W_out`` that round t sampled, after
+        TRAIN and before AGGREGATE, on the current stream (a few torch ops on at most f * M rows)."""
+        ids, attack, scale, seed = self.byz
+        rows = ids if self.sched is None else np.intersect1d(ids, self.sched[t])
+        if len(rows) == 0:
+            return
+        idx = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.W_g.device)
+        W = self.trainer.W_out
+        if attack == 'sign_flip':
+            W[idx] = self.W_g - scale * (W[idx] - self.W_g)
+        elif attack == 'gaussian':
+            z = byzantine_noise(seed, t, (len(rows), self.C, self.D)).to(self.W_g.device)
+            W[idx, :, :self.D] = self.W_g[:, :self.D] + scale * z
+        else:
+            W[idx, :, :self.D] = float('nan')
+
     def _mask_unsampled(self, hist):
         """hist [R, N, 2] of every client's OWN model per round: under partial participation a
         copy with NaN for the clients that did not train in a round (their W_out rows are stale)."""
@@ -923,6 +1036,10 @@ class Federation:
                     norms[t, S] = nh[t, :len(S)]
                 self.stats['update_norms'] = norms
                 self.stats['qffl_coef'] = self.qf_hc[:R].cpu().numpy()
+            if self.robust:
+                self.stats['trim_count'] = np.asarray(self.rb_b[:R], dtype=np.int64)
+                if self.byz is not None:
+                    self.stats['byzantine_ids'] = self.byz[0].copy()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -1095,6 +1212,53 @@ def QFedAvg(X_train, y_train, X_test, y_test, type='classification', num_classes
                 prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
                 options=options, participation=participation, sample_seed=sample_seed, weighting=weighting,
                 qffl=dict(q=q, lipschitz=lipschitz))
+
+
+def FedRobust(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+              batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, rule='median',
+              trim=0.1, byzantine=None, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """Robust aggregation (Yin, Chen, Ramchandran, Bartlett, ICML 2018; not in the reference): FedAvg's
+    positional list, clients always parallel.  Local training is FedAvg's launch unchanged -- both
+    tasks, ``prox=True``, any ``batch_size`` the task's trainer accepts, ``participation`` -- and the server
+    step is fs_aggregate_robust: per parameter, over the round's M clients, the b smallest and b largest
+    values are dropped and the rest averaged, unweighted.  ``rule='median'``: b = (M - 1) // 2;
+    ``'trimmed_mean'``: b = floor(trim * M), clamped so that 2b < M; ``'mean'``: b = 0, the uniform
+    mean (no protection: the baseline an attack is shown against).  Up to b clients per side may
+    return arbitrary bits, NaN and Inf included.  ``byzantine=dict(ids=... | fraction=f, attack='sign_flip'
+    | 'gaussian' | 'nan', scale=1.0, seed=0)`` makes those clients misbehave: their rows of the
+    clients x params buffer are overwritten between TRAIN and AGGREGATE in the rounds that sample
+    them, with W_g - scale (W_k - W_g), W_g + scale N(0, 1) (``byzantine_noise(seed, t, ...)``) or NaN;
+    with ``fraction`` the ids are fixed once from ``seed``.  The global generator is consumed exactly
+    as by ``FedAvg(clients='parallel')`` with the same ``participation``, and ``train_loss`` is FedAvg's
+    (the clients' own training losses, the corrupted ones' included).  ``stats['trim_count']`` [R] int64,
+    ``stats['byzantine_ids']`` the corrupted ids.  ValueError for ``trim`` outside [0, 0.5), an unknown
+    ``rule``, a bad ``byzantine`` or a round whose M is 0 or above ``engine.robust_max_m()``;
+    NotImplementedError over more than one torch.distributed rank."""
+    _check_robust(rule, trim)
+    byzantine_plan(len(y_train), byzantine)
+    return _run('fedrobust', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed,
+                robust=dict(rule=rule, trim=trim, byzantine=byzantine))
+
+
+def FedMedian(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+              batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, byzantine=None,
+              stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """``FedRobust(rule='median')``: the coordinate-wise median of the round's clients."""
+    return FedRobust(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                     lambda_reg_if, lambda_reg, round, rule='median', byzantine=byzantine, stats=stats,
+                     verbose=verbose, options=options, participation=participation, sample_seed=sample_seed)
+
+
+def FedTrimmedMean(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+                   batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, trim=0.1,
+                   byzantine=None, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """``FedRobust(rule='trimmed_mean')``: the coordinate-wise ``trim``-trimmed mean of the round's clients."""
+    return FedRobust(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                     lambda_reg_if, lambda_reg, round, rule='trimmed_mean', trim=trim, byzantine=byzantine,
+                     stats=stats, verbose=verbose, options=options, participation=participation,
+                     sample_seed=sample_seed)
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
