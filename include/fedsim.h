@@ -518,6 +518,79 @@ int fs_aggregate_robust(const float* d_W_all, int64_t stride, const int32_t* d_s
 int fs_aggregate_robust_max_m(void);
 
 /* ------------------------------------------------------------------------- *
+ * Krum and Multi-Krum (Blanchard, El Mhamdi, Guerraoui, Stainer, NeurIPS 2017): robust aggregation
+ * by the pairwise distances of the rows.  Additive to ABI 23: the entry points below,
+ * FS_ABI_VERSION unchanged.
+ *
+ * The rule, over the round's M rows W_k (k the position in d_sel, NULL: rows 0..M-1) of d_W_all,
+ * each of len floats, the round-start model x = d_x [len], a Byzantine bound f and a pick count m:
+ *   Centring.  U_k = fl(W_k - x), elementwise in float as fs_aggregate_qffl forms it.
+ *   Distances. G_ab = U_a . U_b;  D_ab = max(0, fl(fl(G_aa + G_bb) - 2 G_ab)) for a != b, D_aa = 0;
+ *     a D_ab that comes out NaN or +-Inf (NaN or Inf rows, overflow) is stored as +Inf.  One
+ *     triangle is computed and mirrored: D_ab == D_ba bitwise.
+ *   Score.    s_a = the sum, in double, of the n = M - f - 2 smallest of {D_ab : b != a}; a itself is
+ *     left out by index, not by value.  Values that tie at the threshold are equal floats: which
+ *     copies are kept cannot matter.
+ *   Pick.     The m rows with the smallest (s_a, a), lexicographic (a score's bits order it: it is
+ *     >= 0).  m = 1 is Krum, m = M - f the one-shot Multi-Krum.  d_pick [m] holds their row ids of
+ *     d_W_all (d_sel[a], not a), in ascending position a -- ascending id when d_sel ascends.
+ *   Output.   d_out = bitwise what fs_aggregate_sel(d_W_all, d_pick, q == f32(1 / m), m, ...) returns
+ *     with the same chunks, d_agg_ws and agg_ws_floats; for m = 1 the picked row's bits.
+ *   With at most f bad rows of arbitrary bits every good row has M - 1 - f >= n finite distances,
+ *   hence a finite score; a row holding NaN or Inf scores +Inf and is never picked while m rows
+ *   with finite scores exist.
+ *
+ * fs_krum_distances: D [M][ldD], ldD = (M + 3) & ~3 (the padding columns are not written), from
+ * the gathered rows and x.  Summation order of G_ab (float, v_mfma_f32_32x32x2_f32, no other
+ * precision): the len axis is cut into S slices of kc * 32 consecutive elements (S, kc from
+ * fs_krum_split: a function of M and len only; the last slice may be shorter, and is padded with
+ * exact zeros to a multiple of 32).  Inside a slice one accumulator starts at 0 and takes, K-step
+ * by K-step of 32 elements in ascending order, 16 instructions (kq = 0..3 outer, j = 0..3 inner),
+ * each adding the two products at the K-step's offsets 8 kq + j and 8 kq + 4 + j; then
+ * G_ab = ((p_0 + p_1) + p_2) + ... over the slices' partials in ascending order.  A product
+ * therefore passes through at most  min(len, 32 kc) + (S - 1)  additions on its way into G_ab and
+ * two more into D_ab:  n_chain = min(len, 32 kc) + S + 1 <= len + 2,  and with
+ * g = n_chain 2^-24 / (1 - n_chain 2^-24)
+ *     | D_ab - ||U_a - U_b||^2 |  <=  2 g (||U_a||^2 + ||U_b||^2) + 2^-24 ||U_a - U_b||^2
+ * (a-priori; tests/test_gpu_krum_kernels.py holds the kernel to it).  Two launches: the partial
+ * Gram tiles into d_ws (fs_krum_distances_ws_bytes(M, len) bytes; enough for every M' <= M too),
+ * then their fixed-order reduction and D.  No centred copy of the rows is written; rows outside
+ * d_sel are never read.
+ *
+ * fs_krum_select: d_score [M] (double) and d_pick [m] from D [M][ldD] alone (d_sel, NULL: the
+ * identity, only maps positions to ids; d_q, may be NULL: [m] floats set to f32(1 / m); d_rank: M
+ * ints of scratch, left holding every row's rank under (score, position)).  The n-th
+ * smallest t of row a's D_ab, b != a, by a radix select over the raw bits (D >= 0 or +Inf: the
+ * bits are ordered); c = n - #{b != a : D_ab < t} copies of it are kept.  Summation order of s_a
+ * (IEEE double): slice s (0 <= s < 256) = 0.0 + the D_ab < t, b != a, at b = s, s + 256, ... in
+ * ascending b; the slices joined by the pairwise tree p[j] += p[j + h] for j = 0, 2h, 4h, ...,
+ * h = 1, 2, 4, ... < 256;  s_a = tree + (double)c * (double)t.  tests/krum_restatement.py restates
+ * it in numpy; the kernels equal it bit for bit.  Three launches (scores; ranks; pick).
+ *
+ * fs_aggregate_krum: the two stages and the gathered fold on `stream`, six or seven launches.
+ * d_ws: fs_aggregate_krum_ws_bytes(M, len) bytes (enough for every M' <= M too); D stands at its
+ * start ([M][ldD] floats) once the call has run.  d_agg_ws / agg_ws_floats / chunks are
+ * fs_aggregate_sel's.  d_x may be d_out: it is read by the first launch only.  No global atomics,
+ * no cross-workgroup wait, no allocation, no host synchronisation; the same bits on every call
+ * and for the same rows gathered from a larger buffer.
+ * FS_EINVAL, with nothing launched, for M < 3, f < 0, M - f - 2 < 1, m < 1 or m > M - f,
+ * M > fs_aggregate_krum_max_m(), len or stride no multiple of 4, stride < len, a workspace that
+ * is too small or a null pointer (d_sel, d_agg_ws and fs_krum_select's d_q may be NULL).
+ * fs_aggregate_krum_max_m: 5120 (>= fs_aggregate_robust_max_m(): a row of D in one CU's LDS).
+ * ------------------------------------------------------------------------- */
+int fs_aggregate_krum_max_m(void);
+int fs_krum_split(int M, int64_t len, int* splits, int* ksteps);
+int64_t fs_krum_distances_ws_bytes(int M, int64_t len);
+int64_t fs_aggregate_krum_ws_bytes(int M, int64_t len);
+int fs_krum_distances(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                      const float* d_x, float* d_D, void* d_ws, int64_t ws_bytes, void* stream);
+int fs_krum_select(const float* d_D, int M, int f, int m, const int32_t* d_sel, double* d_score, int32_t* d_pick,
+                   float* d_q, int32_t* d_rank, void* stream);
+int fs_aggregate_krum(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                      const float* d_x, int f, int m, float* d_out, int32_t* d_pick, double* d_score, void* d_ws,
+                      int64_t ws_bytes, float* d_agg_ws, int64_t agg_ws_floats, int chunks, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -974,6 +1047,24 @@ int fs_plan_set_qffl(fs_plan* plan, int on, const float* d_g, double Lc, float* 
 #define FS_ROBUST_TRIMMED_MEAN 1
 #define FS_ROBUST_MEDIAN 2
 int fs_plan_set_robust(fs_plan* plan, int on, int mode, double trim);
+
+/* (additive to ABI 23) Krum / Multi-Krum on this plan's AGGREGATE phase.  Host state read when the
+ * next round call enqueues, as fs_plan_set_robust's.  on = 1: AGGREGATE launches fs_aggregate_krum
+ * over the round's rows of d_W_out (all N, or the subset call's M ids) with x = d_W_g into d_W_g,
+ * with the pending finaliser of a deferred evaluation on its fold.  f = min(floor(f_frac * M),
+ * (M - 3) / 2) in double from the round's own client count M; m_mode 1: m = 1 (Krum), 0: m = M - f
+ * (Multi-Krum), any other count: min(m_mode, M - f).  d_pick [N] int32 and d_score [N] double take
+ * the round's picked ids (the first m entries) and scores (by position); d_ws of ws_bytes >=
+ * fs_aggregate_krum_ws_bytes(N, C * ld) bytes, D at its start.  The round's weights are not read.
+ * TRAIN and EVAL are unchanged: every training form, the prox term, loss = 1, B > 64 and subset
+ * rounds work as without it; a subset round of M < 3 clients fails with FS_EINVAL when it
+ * enqueues.  on = 0 restores the plain aggregate.  FS_EINVAL for a chained plan, N < 3,
+ * N > fs_aggregate_krum_max_m(), f_frac outside [0, 0.5), m_mode < 0, a null buffer, a workspace
+ * that is too small, a nova mode other than 0, SCAFFOLD on, a server-optimizer rule set, q-FedAvg
+ * on or a robust aggregate on; fs_plan_set_nova, fs_plan_set_scaffold, fs_plan_set_server_opt,
+ * fs_plan_set_qffl and fs_plan_set_robust refuse in turn while it is on. */
+int fs_plan_set_krum(fs_plan* plan, int on, double f_frac, int m_mode, int32_t* d_pick, double* d_score, void* d_ws,
+                     int64_t ws_bytes);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

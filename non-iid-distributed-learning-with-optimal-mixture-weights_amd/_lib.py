@@ -70,6 +70,20 @@ _SIGS = {
                                       C.c_void_p]),
     'fs_aggregate_robust_max_m': (C.c_int, []),
     'fs_plan_set_robust': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    # Krum / Multi-Krum (additive to ABI 23)
+    'fs_aggregate_krum_max_m': (C.c_int, []),
+    'fs_krum_split': (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'fs_krum_distances_ws_bytes': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_aggregate_krum_ws_bytes': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_krum_distances': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_krum_select': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fs_aggregate_krum': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_int, C.c_void_p]),
+    'fs_plan_set_krum': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -367,6 +381,7 @@ KERNEL_SOURCES = {
     'aggregate_opt': ('aggregate_opt.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_qffl': ('aggregate_qffl.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'lanes.h', 'common.h'),
     'aggregate_robust': ('aggregate_robust.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
+    'aggregate_krum': ('aggregate_krum.hip', 'aggregate_sel.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
 }
 
 

@@ -47,4 +47,11 @@ int64_t aggregate_qffl_ws_doubles_upto(int N, int64_t len);
 int aggregate_robust_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len, int b,
                             float* d_out, const EvalFinalize* fin, hipStream_t st);
 
+// fs_aggregate_krum (aggregate_krum.hip) with an optional finaliser, which rides on its gathered fold
+int aggregate_krum_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                          const float* d_x, int f, int m, float* d_out, int32_t* d_pick, double* d_score, void* d_ws,
+                          int64_t ws_bytes, float* d_agg_ws, int64_t agg_ws_floats, int chunks,
+                          const EvalFinalize* fin, hipStream_t st);
+int64_t aggregate_krum_ws_bytes(int M, int64_t len);
+
 }  // namespace fs

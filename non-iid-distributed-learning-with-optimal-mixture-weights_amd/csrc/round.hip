@@ -45,6 +45,11 @@
 // Robust aggregation (additive to ABI 23, fs_plan_set_robust): AGGREGATE launches fs_aggregate_robust
 // (aggregate_robust.hip), the coordinate-wise trimmed mean or median of the round's rows into
 // d_W_g; the round's weights are not read.  TRAIN is untouched, and the finaliser rides on it.
+//
+// Krum / Multi-Krum (additive to ABI 23, fs_plan_set_krum): AGGREGATE launches fs_aggregate_krum
+// (aggregate_krum.hip), the rows' pairwise distances, the scores, the pick and the gathered fold of
+// the picked rows into d_W_g; the weights are not read.  TRAIN is untouched, and the finaliser
+// rides on the fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -206,6 +211,14 @@ struct fs_plan {
   // fs_plan_set_robust: AGGREGATE is fs_aggregate_robust (0 off, FS_ROBUST_*)
   int robust = 0;
   double rb_trim = 0.0;
+  // fs_plan_set_krum: AGGREGATE is fs_aggregate_krum
+  int krum = 0;
+  double kr_f = 0.0;
+  int kr_m = 0;                       // 1 Krum, 0 M - f, else a count
+  int32_t* kr_pick = nullptr;         // [N]
+  double* kr_score = nullptr;         // [N]
+  void* kr_ws = nullptr;
+  int64_t kr_ws_bytes = 0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -864,6 +877,12 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       // b from the round's own client count, so that 2b < M
       const int b = p->robust == FS_ROBUST_MEDIAN ? (M - 1) / 2 : std::min((int)std::floor(p->rb_trim * (double)M), (M - 1) / 2);
       rc = fs::aggregate_robust_launch(d.d_W_out, len, sel, M, len, b, d.d_W_g, f, st);
+    } else if (p->krum) {
+      // f and m from the round's own client count (M < 3: refused by the launch)
+      const int kf = std::max(0, std::min((int)std::floor(p->kr_f * (double)M), (M - 3) / 2));
+      const int km = p->kr_m == 1 ? 1 : p->kr_m == 0 ? M - kf : std::min(p->kr_m, M - kf);
+      rc = fs::aggregate_krum_launch(d.d_W_out, len, sel, M, len, d.d_W_g, kf, km, d.d_W_g, p->kr_pick, p->kr_score,
+                                     p->kr_ws, p->kr_ws_bytes, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
     } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
@@ -902,6 +921,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
              "a FedNova aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(mode == 0 || !p->qffl, "a FedNova aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(mode == 0 || !p->robust, "a FedNova aggregate and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(mode == 0 || !p->krum, "a FedNova aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -934,6 +954,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(p->opt_rule == 0, "SCAFFOLD and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->qffl, "SCAFFOLD and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "SCAFFOLD and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "SCAFFOLD and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -966,6 +987,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   FS_REQUIRE(!p->scaffold, "a server optimizer and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
   FS_REQUIRE(!p->qffl, "a server optimizer and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "a server optimizer and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "a server optimizer and Krum exclude each other (fs_plan_set_krum(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -1007,6 +1029,7 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   FS_REQUIRE(!p->scaffold, "q-FedAvg and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
   FS_REQUIRE(p->opt_rule == 0, "q-FedAvg and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->robust, "q-FedAvg and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "q-FedAvg and Krum exclude each other (fs_plan_set_krum(0) first)");
   p->qffl = 1;
   p->qf_g = d_g;
   p->qf_L = Lc;
@@ -1040,8 +1063,49 @@ extern "C" int fs_plan_set_robust(fs_plan* p, int on, int mode, double trim) {
   FS_REQUIRE(p->opt_rule == 0,
              "a robust aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->qffl, "a robust aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->krum, "a robust aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   p->robust = mode;
   p->rb_trim = mode == FS_ROBUST_MEDIAN ? 0.0 : trim;
+  return FS_OK;
+}
+
+// Additive to ABI 23: Krum / Multi-Krum on the AGGREGATE phases enqueued from now on (host state, read
+// when a round call enqueues).  on = 1: AGGREGATE launches fs_aggregate_krum over the round's rows
+// with x = d_W_g into d_W_g, f and m from f_frac, m_mode and the round's own client count; the
+// weights are ignored, TRAIN is unchanged.  on = 0: the plain aggregate again.
+extern "C" int fs_plan_set_krum(fs_plan* p, int on, double f_frac, int m_mode, int32_t* d_pick, double* d_score,
+                                void* d_ws, int64_t ws_bytes) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->krum = 0;
+    p->kr_f = 0.0;
+    p->kr_m = 0;
+    p->kr_pick = nullptr;
+    p->kr_score = nullptr;
+    p->kr_ws = nullptr;
+    p->kr_ws_bytes = 0;
+    return FS_OK;
+  }
+  FS_REQUIRE(f_frac >= 0.0 && f_frac < 0.5, "f_frac must be in [0, 0.5)");
+  FS_REQUIRE(m_mode >= 0, "m_mode must be 1 (Krum), 0 (M - f) or a count");
+  FS_REQUIRE(d_pick && d_score && d_ws, "null pointer");
+  FS_REQUIRE(!p->d.chained, "Krum needs parallel clients (a chained client's row holds its predecessors' work)");
+  FS_REQUIRE(p->d.N >= 3, "Krum needs N >= 3");
+  FS_REQUIRE(p->d.N <= fs_aggregate_krum_max_m(), "N is larger than fs_aggregate_krum_max_m()");
+  FS_REQUIRE(ws_bytes >= fs::aggregate_krum_ws_bytes(p->d.N, (int64_t)p->d.C * p->d.ld),
+             "d_ws is too small (fs_aggregate_krum_ws_bytes(N, C * ld))");
+  FS_REQUIRE(p->nova_mode == 0, "Krum and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "Krum and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "Krum and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "Krum and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "Krum and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  p->krum = 1;
+  p->kr_f = f_frac;
+  p->kr_m = m_mode;
+  p->kr_pick = d_pick;
+  p->kr_score = d_score;
+  p->kr_ws = d_ws;
+  p->kr_ws_bytes = ws_bytes;
   return FS_OK;
 }
 

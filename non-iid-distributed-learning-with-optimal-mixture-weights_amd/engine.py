@@ -516,6 +516,27 @@ class RoundPlan:
             raise ValueError("set_robust: mode must be 'trimmed_mean' or 'median'")
         _lib.check(_lib.lib().fs_plan_set_robust(self._h, 1, modes[mode], float(trim)), 'fs_plan_set_robust')
 
+    def set_krum(self, on, f=0.1, m=0, pick=None, score=None, ws=None):
+        """fs_plan_set_krum: Krum / Multi-Krum on the AGGREGATE phases enqueued from now on --
+        fs_aggregate_krum over the round's rows of ``W_out`` with x = ``W_g`` into ``W_g``.  ``f``: the
+        Byzantine fraction in [0, 0.5), f = min(floor(f * M), (M - 3) // 2) with M the round's own
+        client count; ``m``: 1 Krum, 0 Multi-Krum (M - f), else a count clamped to M - f.  ``pick``
+        int32 [N] and ``score`` float64 [N] take every round's picked ids (the first m entries) and
+        scores (by position); ``ws``: ``Aggregator.krum_ws()`` (uint8), the distance matrix at its
+        start.  The weights are ignored, TRAIN and EVAL are unchanged.  ``on`` false restores the plain
+        aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_krum(self._h, 0, 0.0, 0, None, None, None, 0), 'fs_plan_set_krum')
+            self._krum = None
+            return
+        if not (pick is not None and pick.is_cuda and pick.dtype == torch.int32 and pick.is_contiguous()
+                and score is not None and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous()
+                and ws is not None and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+            raise ValueError('set_krum: pick (int32), score (float64) and ws (uint8) must be contiguous device tensors')
+        _lib.check(_lib.lib().fs_plan_set_krum(self._h, 1, float(f), int(m), _lib.ptr(pick), _lib.ptr(score),
+                                               _lib.ptr(ws), ws.numel()), 'fs_plan_set_krum')
+        self._krum = (pick, score, ws)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -706,6 +727,67 @@ class Aggregator:
                                                 _lib.stream_ptr()), 'fs_aggregate_qffl')
         return W_g, S, n, hc
 
+    def krum_ws(self, M=None):
+        """A uint8 workspace for ``run_krum`` / ``krum_distances`` at up to ``M`` rows (None: N):
+        fs_aggregate_krum_ws_bytes, what ``RoundPlan.set_krum`` asks for."""
+        M = self.N if M is None else int(M)
+        return torch.empty(max(16, int(_lib.lib().fs_aggregate_krum_ws_bytes(M, self.len))), dtype=torch.uint8,
+                           device=self.ws.device)
+
+    def _krum_rows(self, what, W_all, x, sel, check):
+        M = self.N if sel is None else int(sel.numel())
+        if not (W_all.is_cuda and W_all.dtype == torch.float32 and W_all.is_contiguous() and x.is_cuda
+                and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.len):
+            raise ValueError('%s: W_all and x must be contiguous float32 device tensors' % what)
+        if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and M >= 1):
+            raise ValueError('%s: sel must be a contiguous, non-empty int32 device tensor' % what)
+        rows = W_all.numel() // self.len
+        if sel is None and M > rows:
+            raise ValueError('%s: W_all has fewer than N rows' % what)
+        if M > krum_max_m():
+            raise ValueError('%s: M = %d is above fs_aggregate_krum_max_m() = %d' % (what, M, krum_max_m()))
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('%s: sel must index rows of W_all, [0, %d)' % (what, rows))
+        return M
+
+    def krum_distances(self, W_all, x, D, ws, sel=None, check=True):
+        """fs_krum_distances: ``D`` float32 [M, krum_ldd(M)] = the squared distances between the rows
+        ``sel`` of ``W_all`` (None: rows 0..N-1), each centred on ``x`` first (include/fedsim.h: the order
+        and the bound).  ``ws``: ``krum_ws()``.  Exactly symmetric, a zero diagonal, +Inf where a
+        distance is not finite; the padding columns are left as they are."""
+        M = self._krum_rows('krum_distances', W_all, x, sel, check)
+        if not (D.is_cuda and D.dtype == torch.float32 and D.is_contiguous() and D.numel() >= M * krum_ldd(M)
+                and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+            raise ValueError('krum_distances: D (float32 [M, ldD]) and ws (uint8) must be contiguous device tensors')
+        _lib.check(_lib.lib().fs_krum_distances(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                                self.len, _lib.ptr(x), _lib.ptr(D), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_ptr()), 'fs_krum_distances')
+        return D
+
+    def run_krum(self, W_all, x, f, m, out, pick, score, ws, sel=None, check=True):
+        """fs_aggregate_krum: Krum (``m = 1``) / Multi-Krum over the rows ``sel`` of ``W_all`` (None: rows
+        0..N-1) about the round-start model ``x`` with the Byzantine bound ``f``: the pairwise squared
+        distances of the centred rows, every row's score (the sum of its M - f - 2 smallest distances,
+        float64 into ``score`` [M]), the m rows of the smallest (score, position) (their row ids into
+        ``pick`` [m], int32) and their uniform mean into ``out`` -- bitwise ``run_sel(W_all, pick, 1/m)``.
+        ``out`` may be ``x``.  ``ws``: ``krum_ws()``; the distance matrix stands at its start afterwards
+        (float32 [M, krum_ldd(M)]).  ``check`` as in ``run_sel``."""
+        M = self._krum_rows('run_krum', W_all, x, sel, check)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= self.len
+                and pick.is_cuda and pick.dtype == torch.int32 and pick.is_contiguous() and pick.numel() >= max(1, int(m))
+                and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous() and score.numel() >= M
+                and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+            raise ValueError('run_krum: out (float32), pick (int32 [m]), score (float64 [M]) and ws (uint8) must be '
+                             'contiguous device tensors')
+        _lib.check(_lib.lib().fs_aggregate_krum(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                                self.len, _lib.ptr(x), int(f), int(m), _lib.ptr(out), _lib.ptr(pick),
+                                                _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.ptr(self.ws),
+                                                self.ws.numel(), int(self.chunks), _lib.stream_ptr()),
+                   'fs_aggregate_krum')
+        return out
+
     def run_robust(self, W_all, b, out, sel=None, check=True):
         """fs_aggregate_robust: the coordinate-wise trimmed mean of the rows ``sel`` of ``W_all`` (None:
         rows 0..N-1) with the trim count ``b``, 0 <= 2b < M: per coordinate the b smallest and the b
@@ -732,6 +814,51 @@ class Aggregator:
                                                   self.len, int(b), _lib.ptr(out), _lib.stream_ptr()),
                    'fs_aggregate_robust')
         return out
+
+
+def krum_max_m():
+    """fs_aggregate_krum_max_m: the largest number of rows ``Aggregator.run_krum`` accepts."""
+    return int(_lib.lib().fs_aggregate_krum_max_m())
+
+
+def krum_split(M, length):
+    """fs_krum_split: (slices of the len axis, K-steps of 32 elements per slice) of fs_krum_distances at
+    M rows of ``length`` floats -- its summation order (include/fedsim.h)."""
+    import ctypes
+    s, k = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().fs_krum_split(int(M), int(length), ctypes.byref(s), ctypes.byref(k)), 'fs_krum_split')
+    return s.value, k.value
+
+
+def krum_select(D, M, f, m, score, pick, q=None, sel=None, rank=None):
+    """fs_krum_select: from the float32 distance matrix ``D`` [M, krum_ldd(M)] alone, every row's score
+    (float64 ``score`` [M]: the sum of its M - f - 2 smallest distances to the others) and the row ids of
+    the ``m`` smallest (score, position) in ascending position (int32 ``pick`` [m]; ``sel`` int32 [M] maps
+    positions to ids, None: the identity).  ``q`` float32 [m], if given, is set to f32(1 / m); ``rank``
+    int32 [M] of scratch (None: allocated here), left holding every row's rank."""
+    M, m = int(M), int(m)
+    if rank is None:
+        rank = torch.empty(max(1, M), dtype=torch.int32, device=D.device)
+    if not (rank.is_cuda and rank.dtype == torch.int32 and rank.is_contiguous() and rank.numel() >= M):
+        raise ValueError('krum_select: rank must be a contiguous int32 device tensor of M elements')
+    if not (D.is_cuda and D.dtype == torch.float32 and D.is_contiguous() and D.numel() >= M * krum_ldd(M)
+            and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous() and score.numel() >= M
+            and pick.is_cuda and pick.dtype == torch.int32 and pick.is_contiguous() and pick.numel() >= max(1, m)):
+        raise ValueError('krum_select: D (float32 [M, ldD]), score (float64 [M]) and pick (int32 [m]) must be '
+                         'contiguous device tensors')
+    if q is not None and not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.numel() >= max(1, m)):
+        raise ValueError('krum_select: q must be a contiguous float32 device tensor of m elements')
+    if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() >= M):
+        raise ValueError('krum_select: sel must be a contiguous int32 device tensor of M elements')
+    _lib.check(_lib.lib().fs_krum_select(_lib.ptr(D), M, int(f), m, None if sel is None else _lib.ptr(sel),
+                                         _lib.ptr(score), _lib.ptr(pick), None if q is None else _lib.ptr(q),
+                                         _lib.ptr(rank), _lib.stream_ptr()), 'fs_krum_select')
+    return score, pick
+
+
+def krum_ldd(M):
+    """The row pitch of fs_krum_distances' matrix: M rounded up to 4."""
+    return (int(M) + 3) & ~3
 
 
 def robust_max_m():

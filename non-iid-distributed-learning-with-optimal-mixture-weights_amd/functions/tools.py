@@ -448,6 +448,45 @@ def _check_robust_rounds(Ms, max_m):
                              % (t, M, max_m))
 
 
+def _check_krum(f, m, clients='parallel'):
+    """FedKrum's keyword checks (host only: before any device is touched)."""
+    if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)):
+        raise ValueError('f must be a fraction in [0, 0.5) or an int count >= 0')
+    if isinstance(f, (int, np.integer)):
+        if f < 0:
+            raise ValueError('f must be a fraction in [0, 0.5) or an int count >= 0')
+    elif not (0.0 <= float(f) < 0.5):
+        raise ValueError('f must be a fraction in [0, 0.5) or an int count >= 0')
+    if m is not None and (isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1):
+        raise ValueError('m must be None (M - f) or an int count >= 1')
+    if clients != 'parallel':
+        raise ValueError("FedKrum needs clients='parallel': a chained client's row holds its predecessors' work")
+
+
+def krum_counts(f, m, M):
+    """(f, m) of a round of M clients: ``f`` an int count as it is, a fraction floor(f * M) in float64;
+    ``m`` None: M - f.  ValueError unless M >= 2f + 3 (the paper's condition) and 1 <= m <= M - f."""
+    M = int(M)
+    fc = int(f) if isinstance(f, (int, np.integer)) else int(math.floor(float(f) * float(M)))
+    if M < 2 * fc + 3:
+        raise ValueError('FedKrum: a round of M = %d clients with f = %d needs M >= 2f + 3' % (M, fc))
+    mc = M - fc if m is None else int(m)
+    if not 1 <= mc <= M - fc:
+        raise ValueError('FedKrum: m = %d is outside [1, M - f] = [1, %d]' % (mc, M - fc))
+    return fc, mc
+
+
+def _check_krum_rounds(Ms, f, m, max_m):
+    """The (f, m) of every round; ValueError for a round above ``max_m`` clients or against krum_counts."""
+    out = []
+    for t, M in enumerate(Ms):
+        if M > max_m:
+            raise ValueError('FedKrum: round %d has M = %d clients, above fs_aggregate_krum_max_m() = %d'
+                             % (t, M, max_m))
+        out.append(krum_counts(f, m, M))
+    return out
+
+
 def byzantine_plan(N, byzantine):
     """``byzantine=`` checked and resolved (host only): None, or (sorted int64 ids, attack, scale, seed).
     ``ids``: the client ids given; ``fraction``: floor(fraction * N) ids fixed once from ``seed``
@@ -492,9 +531,16 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None):
+                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None):
         self.robust = algo == 'fedrobust'
         self.byz = None
+        self.krum = algo == 'fedkrum'
+        if self.krum:
+            # krum: dict(f=, m=, byzantine=) (tools.FedKrum)
+            kr = dict(krum or {})
+            self.kr_f, self.kr_m = kr.get('f', 0.1), kr.get('m')
+            _check_krum(self.kr_f, self.kr_m, clients)
+            self.byz = byzantine_plan(len(y_train), kr.get('byzantine'))
         if self.robust:
             # robust: dict(rule=, trim=, byzantine=) (tools.FedRobust)
             rb = dict(robust or {})
@@ -549,7 +595,7 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust'):
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust', 'fedkrum'):
                 raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
                                           'FedOpt, QFedAvg and FedRobust only')
             if self.chained:
@@ -575,6 +621,12 @@ class Federation:
             self.rb_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
             _check_robust_rounds(self.rb_M, engine.robust_max_m())
             self.rb_b = [robust_trim_count(self.rb_rule, self.rb_trim, M) for M in self.rb_M]
+        if self.krum:
+            if nranks > 1:
+                # (the distances need all clients' rows)
+                raise NotImplementedError('FedKrum over more than one torch.distributed rank is not implemented')
+            self.kr_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
+            self.kr_fm = _check_krum_rounds(self.kr_M, self.kr_f, self.kr_m, engine.krum_max_m())
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -783,6 +835,12 @@ class Federation:
             # client count inside the plan ('mean': trim 0)
             self.plan.set_robust(True, 'median' if self.rb_rule == 'median' else 'trimmed_mean',
                                  self.rb_trim if self.rb_rule == 'trimmed_mean' else 0.0)
+        if self.krum:
+            # FedAvg's round with fs_aggregate_krum as its aggregate; every round's ids and scores land in
+            # that round's row of the two histories (the setter is called again before each round)
+            self.kr_pick = torch.full((R, self.N), -1, dtype=torch.int32, device=dev)
+            self.kr_score = torch.full((R, self.N), float('nan'), dtype=torch.float64, device=dev)
+            self.kr_ws = self.agg.krum_ws()
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -860,6 +918,10 @@ class Federation:
                                                         self.qf_u, self.qf_g,
                                                         None if self.sched is None else self.sel_dev[t][:M_t]))
             self.plan.set_qffl(True, self.qf_g, self.qf_L[t], self.qf_S, self.qf_n[t], self.qf_hc[t], self.qf_nws)
+        if self.krum:
+            # (f + 1/2) / M: the fraction whose floor(. * M) is this round's f inside the plan
+            f_t, m_t = self.kr_fm[t]
+            self.plan.set_krum(True, (f_t + 0.5) / self.kr_M[t], m_t, self.kr_pick[t], self.kr_score[t], self.kr_ws)
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -1038,6 +1100,17 @@ class Federation:
                 self.stats['qffl_coef'] = self.qf_hc[:R].cpu().numpy()
             if self.robust:
                 self.stats['trim_count'] = np.asarray(self.rb_b[:R], dtype=np.int64)
+                if self.byz is not None:
+                    self.stats['byzantine_ids'] = self.byz[0].copy()
+            if self.krum:
+                self.stats['krum_f'] = np.asarray([f for f, _ in self.kr_fm[:R]], dtype=np.int64)
+                pk, sh = self.kr_pick[:R].cpu().numpy(), self.kr_score[:R].cpu().numpy()
+                self.stats['krum_selected'] = [np.sort(pk[t, :self.kr_fm[t][1]].astype(np.int64)) for t in range(R)]
+                scores = np.full((R, self.N), np.nan)
+                for t in range(R):
+                    S = np.arange(self.N) if self.sched is None else self.sched[t]
+                    scores[t, S] = sh[t, :len(S)]
+                self.stats['krum_scores'] = scores
                 if self.byz is not None:
                     self.stats['byzantine_ids'] = self.byz[0].copy()
             if self.mixture is not None:
@@ -1259,6 +1332,50 @@ def FedTrimmedMean(X_train, y_train, X_test, y_test, type='classification', num_
                      lambda_reg_if, lambda_reg, round, rule='trimmed_mean', trim=trim, byzantine=byzantine,
                      stats=stats, verbose=verbose, options=options, participation=participation,
                      sample_seed=sample_seed)
+
+
+def FedKrum(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, f=0.1, m=None,
+            byzantine=None, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """Krum and Multi-Krum (Blanchard, El Mhamdi, Guerraoui, Stainer, NeurIPS 2017; not in the reference):
+    FedAvg's positional list, clients always parallel.  Local training is FedAvg's launch unchanged -- both
+    tasks, ``prox=True``, any ``batch_size`` the task's trainer accepts, ``participation`` -- and the server
+    step is fs_aggregate_krum: the squared distances between the round's M updates W_k - W_g, every
+    client's score (the sum of its M - f - 2 smallest distances), and the unweighted mean of the m clients
+    with the smallest (score, id).  ``f``: the number of clients that may return arbitrary bits, an int
+    count or a fraction in [0, 0.5) (floor(f * M) of the round's own M); ``m``: None for M - f (the
+    one-shot Multi-Krum), 1 for Krum, or a count.  ``byzantine=`` as in ``FedRobust``.  The global generator
+    is consumed exactly as by ``FedAvg(clients='parallel')`` with the same ``participation``, and
+    ``train_loss`` is FedAvg's.  ``stats['krum_f']`` [R] int64, ``stats['krum_selected']`` R sorted id arrays,
+    ``stats['krum_scores']`` [R, N] float64 (NaN where a client was not sampled), ``stats['byzantine_ids']``.
+    ValueError for a bad ``f`` or ``m``, a bad ``byzantine``, a round with M < 2f + 3 or m > M - f, or M above
+    ``engine.krum_max_m()``; NotImplementedError over more than one torch.distributed rank."""
+    _check_krum(f, m)
+    byzantine_plan(len(y_train), byzantine)
+    if participation is None:
+        krum_counts(f, m, len(y_train))
+    return _run('fedkrum', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed,
+                krum=dict(f=f, m=m, byzantine=byzantine))
+
+
+def Krum(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+         batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, f=0.1, byzantine=None,
+         stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """``FedKrum(m=1)``: the one client whose update lies closest to its M - f - 2 nearest neighbours."""
+    return FedKrum(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                   lambda_reg_if, lambda_reg, round, f=f, m=1, byzantine=byzantine, stats=stats, verbose=verbose,
+                   options=options, participation=participation, sample_seed=sample_seed)
+
+
+def MultiKrum(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+              batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, f=0.1,
+              byzantine=None, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """``FedKrum(m=None)``: the mean of the M - f clients with the smallest scores."""
+    return FedKrum(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
+                   lambda_reg_if, lambda_reg, round, f=f, m=None, byzantine=byzantine, stats=stats, verbose=verbose,
+                   options=options, participation=participation, sample_seed=sample_seed)
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
