@@ -591,6 +591,75 @@ int fs_aggregate_krum(const float* d_W_all, int64_t stride, const int32_t* d_sel
                       int64_t ws_bytes, float* d_agg_ws, int64_t agg_ws_floats, int chunks, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * RFA (Pillutla, Kakade, Harchaoui, IEEE TSP 2022): the geometric median of the rows by T
+ * smoothed Weiszfeld iterations.  Additive to ABI 23: the entry points below, FS_ABI_VERSION
+ * unchanged.
+ *
+ * The rule, over the round's M rows W_k (k the position in d_sel, NULL: rows 0..M-1) of d_W_all,
+ * each of len floats, the round-start model x = d_x [len], weights alpha_k >= 0 (d_alpha [M]
+ * floats), a smoothing nu > 0, an iteration count 0 <= T <= FS_RFA_MAX_ITERS fixed by the caller and
+ * init = FS_RFA_INIT_START (v0 = x) or FS_RFA_INIT_MEAN.  W = fs_rfa_width(M) (32, 16 or 8: a
+ * function of M only) cuts the len axis into stripes of W consecutive columns, the last one
+ * possibly shorter; all arithmetic is IEEE, nothing is contracted.
+ *   Distance.  d_k(v) = sqrt(d2_k), d2_k = sum_i (double)e_i * (double)e_i with e_i = fl(W_k[i] - v[i])
+ *     in float, as fs_aggregate_qffl forms it.  Order: a stripe's partial = 0.0 + its terms in
+ *     ascending i; slice s (0 <= s < 32) = 0.0 + the partials of the stripes s, s + 32, ... in
+ *     ascending order; the slices joined by the pairwise tree p[j] += p[j + h] for j = 0, 2h, 4h,
+ *     ..., h = 1, 2, 4, ... < 32.  The sum cannot overflow in double; d_k is NaN or +Inf exactly
+ *     when the row holds NaN or Inf or a float difference overflows.  Such a row is "not finite".
+ *   Weights.   beta_k = (double)alpha_k / max(nu, d_k) when d_k is finite, else 0 (the weighted-mean
+ *     step of INIT_MEAN: beta_k = (double)alpha_k when d_k is finite, else 0).  B = sum_k beta_k:
+ *     slice s (0 <= s < 256) = 0.0 + beta_k at k = s, s + 256, ... ascending, the 256 slices joined by
+ *     the same tree (h < 256).  b_k = (float)(beta_k / B); every b_k = 0 when B is 0 or not finite
+ *     ("no finite row").  Stateless: a row is judged again at every iteration.
+ *   Fold.      v'[i] = (float)(sum_{k : b_k != 0} (double)b_k * (double)W_k[i]) (the products are
+ *     exact).  Order: slice s (0 <= s < 256 / W) = 0.0 + the terms at k = s, s + 256 / W, ... ascending,
+ *     the slices joined by the same tree (h < 256 / W).  A row with b_k == 0 is skipped by index,
+ *     never multiplied (0 * NaN).  After "no finite row" v' = v bit for bit.
+ *   Objective. g(v) = sum_{k finite} (double)alpha_k * h(d_k), h(d) = d for d > nu, else
+ *     d * d / (2.0 * nu) + nu / 2.0, in B's order; NaN when no row is finite.
+ *   Chain.     Pass 0 takes the distances to x and folds nothing.  INIT_MEAN: one fused step with
+ *     the weighted-mean weights over the rows pass 0 found finite gives v0.  Then T fused steps,
+ *     each with the weights from the distances to the iterate before it.  d_out = v_T (T = 0: x, or
+ *     v0).  d_dist [M] (double): the distances to d_out.  d_b [M]: the weights of the last fold (no
+ *     fold at all, T = 0 from INIT_START: the weights pass 0 gave).  d_obj [T + 2] (double): g at
+ *     x, at v0 (INIT_MEAN only), at v_1 .. v_T, in this order; the slots the chain does not reach
+ *     hold NaN.
+ *
+ * fs_rfa_step: one iteration from one read of the rows.  d_b == NULL (then d_flag == NULL): pass 0,
+ * d_v_out = d_v and the distances to it.  Else d_v_out = the fold with d_b (d_flag[0] != 0: d_v
+ * instead), and the distances to d_v_out.  d_part [stripes][M] doubles takes the stripes' partials
+ * (stripes = ceil(len / W)).  d_v_out may be d_v.
+ * fs_rfa_weights: d_part reduced into d_d2 [M] (d_part == NULL: d_d2 as given), then d_dist, d_b,
+ * d_obj[0] and d_flag[0] (1: no finite row) as above; mean = 1 for the weighted-mean weights.  Two
+ * launches (the reduction over the stripes: 8 rows to a workgroup; the weights: one workgroup).
+ * fs_aggregate_rfa: the chain on `stream`, 3 (T + 1) launches, 3 (T + 2) with INIT_MEAN (a step, the
+ * reduction and the weights per stage).  d_ws: fs_aggregate_rfa_ws_bytes(M, len) bytes (enough for
+ * every M' <= M too): the partial table, d2, two iterates, the flag.  d_out may be d_x: x is read
+ * by pass 0 only, which copies it.  No global atomics, no cross-workgroup wait, no allocation, no
+ * host synchronisation; the same bits on every call and for the same rows gathered from a larger
+ * buffer.  tests/rfa_restatement.py restates the rule in numpy; the kernels equal it bit for bit.
+ * FS_EINVAL, with nothing launched, for M < 1, M > fs_aggregate_rfa_max_m(), T outside [0, 32],
+ * nu <= 0 or not finite, an unknown init, len or stride no multiple of 4, stride < len, a workspace
+ * that is too small or a null pointer (d_sel may be NULL).
+ * fs_aggregate_rfa_max_m: 5047 (= fs_aggregate_robust_max_m(): 8 columns of every row in one CU's
+ * LDS); W = 32 up to M = 1261, 16 up to 2523.
+ * ------------------------------------------------------------------------- */
+#define FS_RFA_INIT_START 0
+#define FS_RFA_INIT_MEAN 1
+#define FS_RFA_MAX_ITERS 32
+int fs_aggregate_rfa_max_m(void);
+int fs_rfa_width(int M);
+int64_t fs_aggregate_rfa_ws_bytes(int M, int64_t len);
+int fs_rfa_step(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len, const float* d_v,
+                const float* d_b, const int32_t* d_flag, float* d_v_out, double* d_part, void* stream);
+int fs_rfa_weights(const double* d_part, int M, int64_t len, const float* d_alpha, double nu, int mean, double* d_d2,
+                   double* d_dist, float* d_b, double* d_obj, int32_t* d_flag, void* stream);
+int fs_aggregate_rfa(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                     const float* d_x, const float* d_alpha, int T, double nu, int init, float* d_out, double* d_dist,
+                     float* d_b, double* d_obj, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -1065,6 +1134,23 @@ int fs_plan_set_robust(fs_plan* plan, int on, int mode, double trim);
  * fs_plan_set_qffl and fs_plan_set_robust refuse in turn while it is on. */
 int fs_plan_set_krum(fs_plan* plan, int on, double f_frac, int m_mode, int32_t* d_pick, double* d_score, void* d_ws,
                      int64_t ws_bytes);
+
+/* (additive to ABI 23) RFA on this plan's AGGREGATE phase.  Host state read when the next round
+ * call enqueues, as fs_plan_set_krum's.  on = 1: AGGREGATE launches fs_aggregate_rfa over the
+ * round's rows of d_W_out (all N, or the subset call's M ids) with x = d_W_g into d_W_g, T, nu and
+ * init as given, with the pending finaliser of a deferred evaluation on its last step.  alpha is
+ * the round's weights (d_p_override or the plan's p, the subset call's q: as q-FedAvg takes
+ * them), or f32(1 / M) for every row when uniform is set.  d_dist [N] double, d_b [N] float and
+ * d_obj [T + 2] double take the round's recorded values (by position); d_ws of ws_bytes >=
+ * fs_aggregate_rfa_ws_bytes(N, C * ld) bytes.  TRAIN and EVAL are unchanged: every training form,
+ * the prox term, loss = 1, B > 64 and subset rounds work as without it.  on = 0 restores the plain
+ * aggregate.  FS_EINVAL for a chained plan, N > fs_aggregate_rfa_max_m(), T outside [0, 32],
+ * nu <= 0 or not finite, an unknown init, a null buffer, a workspace that is too small, a nova
+ * mode other than 0, SCAFFOLD on, a server-optimizer rule set, q-FedAvg on, a robust aggregate
+ * on or Krum on; fs_plan_set_nova, fs_plan_set_scaffold, fs_plan_set_server_opt,
+ * fs_plan_set_qffl, fs_plan_set_robust and fs_plan_set_krum refuse in turn while it is on. */
+int fs_plan_set_rfa(fs_plan* plan, int on, int T, double nu, int init, int uniform, double* d_dist, float* d_b,
+                    double* d_obj, void* d_ws, int64_t ws_bytes);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

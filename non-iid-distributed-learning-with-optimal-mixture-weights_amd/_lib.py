@@ -84,6 +84,19 @@ _SIGS = {
                                     C.c_int64, C.c_int, C.c_void_p]),
     'fs_plan_set_krum': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64]),
+    # RFA, the geometric median by Weiszfeld steps (additive to ABI 23)
+    'fs_aggregate_rfa_max_m': (C.c_int, []),
+    'fs_rfa_width': (C.c_int, [C.c_int]),
+    'fs_aggregate_rfa_ws_bytes': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_rfa_step': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fs_rfa_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fs_aggregate_rfa': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_plan_set_rfa': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int64]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -382,6 +395,7 @@ KERNEL_SOURCES = {
     'aggregate_qffl': ('aggregate_qffl.hip', 'aggregate.hip', 'aggregate_sel.h', 'finalize.h', 'lanes.h', 'common.h'),
     'aggregate_robust': ('aggregate_robust.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_krum': ('aggregate_krum.hip', 'aggregate_sel.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
+    'aggregate_rfa': ('aggregate_rfa.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
 }
 
 

@@ -54,4 +54,12 @@ int aggregate_krum_launch(const float* d_W_all, int64_t stride, const int32_t* d
                           const EvalFinalize* fin, hipStream_t st);
 int64_t aggregate_krum_ws_bytes(int M, int64_t len);
 
+// fs_aggregate_rfa (aggregate_rfa.hip) with an optional finaliser, which rides on the chain's last
+// step (d_alpha == nullptr: every row weighs ualpha)
+int aggregate_rfa_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                         const float* d_x, const float* d_alpha, float ualpha, int T, double nu, int init, float* d_out,
+                         double* d_dist, float* d_b, double* d_obj, void* d_ws, int64_t ws_bytes,
+                         const EvalFinalize* fin, hipStream_t st);
+int64_t aggregate_rfa_ws_bytes(int M, int64_t len);
+
 }  // namespace fs

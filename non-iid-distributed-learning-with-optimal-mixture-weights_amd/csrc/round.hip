@@ -50,10 +50,15 @@
 // (aggregate_krum.hip), the rows' pairwise distances, the scores, the pick and the gathered fold of
 // the picked rows into d_W_g; the weights are not read.  TRAIN is untouched, and the finaliser
 // rides on the fold.
+//
+// RFA (additive to ABI 23, fs_plan_set_rfa): AGGREGATE launches fs_aggregate_rfa (aggregate_rfa.hip),
+// T smoothed Weiszfeld iterations over the round's rows from x = d_W_g into d_W_g, under the
+// round's weights or uniform ones.  TRAIN is untouched, and the finaliser rides on the last step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -219,6 +224,15 @@ struct fs_plan {
   double* kr_score = nullptr;         // [N]
   void* kr_ws = nullptr;
   int64_t kr_ws_bytes = 0;
+  // fs_plan_set_rfa: AGGREGATE is fs_aggregate_rfa
+  int rfa = 0;
+  int rf_T = 0, rf_init = 0, rf_uniform = 0;
+  double rf_nu = 0.0;
+  double* rf_dist = nullptr;          // [N]
+  float* rf_b = nullptr;              // [N]
+  double* rf_obj = nullptr;           // [T + 2]
+  void* rf_ws = nullptr;
+  int64_t rf_ws_bytes = 0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -883,6 +897,10 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       const int km = p->kr_m == 1 ? 1 : p->kr_m == 0 ? M - kf : std::min(p->kr_m, M - kf);
       rc = fs::aggregate_krum_launch(d.d_W_out, len, sel, M, len, d.d_W_g, kf, km, d.d_W_g, p->kr_pick, p->kr_score,
                                      p->kr_ws, p->kr_ws_bytes, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
+    } else if (p->rfa) {
+      rc = fs::aggregate_rfa_launch(d.d_W_out, len, sel, M, len, d.d_W_g, p->rf_uniform ? nullptr : pw,
+                                    (float)(1.0 / (double)M), p->rf_T, p->rf_nu, p->rf_init, d.d_W_g, p->rf_dist,
+                                    p->rf_b, p->rf_obj, p->rf_ws, p->rf_ws_bytes, f, st);
     } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
@@ -922,6 +940,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   FS_REQUIRE(mode == 0 || !p->qffl, "a FedNova aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(mode == 0 || !p->robust, "a FedNova aggregate and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(mode == 0 || !p->krum, "a FedNova aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(mode == 0 || !p->rfa, "a FedNova aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -955,6 +974,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(!p->qffl, "SCAFFOLD and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "SCAFFOLD and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "SCAFFOLD and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "SCAFFOLD and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -988,6 +1008,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   FS_REQUIRE(!p->qffl, "a server optimizer and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "a server optimizer and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "a server optimizer and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "a server optimizer and RFA exclude each other (fs_plan_set_rfa(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -1030,6 +1051,7 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   FS_REQUIRE(p->opt_rule == 0, "q-FedAvg and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->robust, "q-FedAvg and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "q-FedAvg and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "q-FedAvg and RFA exclude each other (fs_plan_set_rfa(0) first)");
   p->qffl = 1;
   p->qf_g = d_g;
   p->qf_L = Lc;
@@ -1064,6 +1086,7 @@ extern "C" int fs_plan_set_robust(fs_plan* p, int on, int mode, double trim) {
              "a robust aggregate and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->qffl, "a robust aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->krum, "a robust aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "a robust aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
   p->robust = mode;
   p->rb_trim = mode == FS_ROBUST_MEDIAN ? 0.0 : trim;
   return FS_OK;
@@ -1099,6 +1122,7 @@ extern "C" int fs_plan_set_krum(fs_plan* p, int on, double f_frac, int m_mode, i
   FS_REQUIRE(p->opt_rule == 0, "Krum and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
   FS_REQUIRE(!p->qffl, "Krum and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "Krum and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->rfa, "Krum and RFA exclude each other (fs_plan_set_rfa(0) first)");
   p->krum = 1;
   p->kr_f = f_frac;
   p->kr_m = m_mode;
@@ -1106,6 +1130,51 @@ extern "C" int fs_plan_set_krum(fs_plan* p, int on, double f_frac, int m_mode, i
   p->kr_score = d_score;
   p->kr_ws = d_ws;
   p->kr_ws_bytes = ws_bytes;
+  return FS_OK;
+}
+
+// Additive to ABI 23: RFA on the AGGREGATE phases enqueued from now on (host state, read when a round
+// call enqueues).  on = 1: AGGREGATE launches fs_aggregate_rfa over the round's rows with x = d_W_g
+// into d_W_g under the round's weights (uniform: f32(1 / M)); TRAIN is unchanged.  on = 0: the plain
+// aggregate again.
+extern "C" int fs_plan_set_rfa(fs_plan* p, int on, int T, double nu, int init, int uniform, double* d_dist, float* d_b,
+                               double* d_obj, void* d_ws, int64_t ws_bytes) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->rfa = 0;
+    p->rf_T = p->rf_init = p->rf_uniform = 0;
+    p->rf_nu = 0.0;
+    p->rf_dist = nullptr;
+    p->rf_b = nullptr;
+    p->rf_obj = nullptr;
+    p->rf_ws = nullptr;
+    p->rf_ws_bytes = 0;
+    return FS_OK;
+  }
+  FS_REQUIRE(T >= 0 && T <= FS_RFA_MAX_ITERS, "T must be in [0, 32]");
+  FS_REQUIRE(nu > 0.0 && std::isfinite(nu), "nu must be positive and finite");
+  FS_REQUIRE(init == FS_RFA_INIT_START || init == FS_RFA_INIT_MEAN, "init must be FS_RFA_INIT_START or FS_RFA_INIT_MEAN");
+  FS_REQUIRE(d_dist && d_b && d_obj && d_ws, "null pointer");
+  FS_REQUIRE(!p->d.chained, "RFA needs parallel clients (a chained client's row holds its predecessors' work)");
+  FS_REQUIRE(p->d.N <= fs_aggregate_rfa_max_m(), "N is larger than fs_aggregate_rfa_max_m()");
+  FS_REQUIRE(ws_bytes >= fs::aggregate_rfa_ws_bytes(p->d.N, (int64_t)p->d.C * p->d.ld),
+             "d_ws is too small (fs_aggregate_rfa_ws_bytes(N, C * ld))");
+  FS_REQUIRE(p->nova_mode == 0, "RFA and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "RFA and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "RFA and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "RFA and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "RFA and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "RFA and Krum exclude each other (fs_plan_set_krum(0) first)");
+  p->rfa = 1;
+  p->rf_T = T;
+  p->rf_nu = nu;
+  p->rf_init = init;
+  p->rf_uniform = uniform ? 1 : 0;
+  p->rf_dist = d_dist;
+  p->rf_b = d_b;
+  p->rf_obj = d_obj;
+  p->rf_ws = d_ws;
+  p->rf_ws_bytes = ws_bytes;
   return FS_OK;
 }
 

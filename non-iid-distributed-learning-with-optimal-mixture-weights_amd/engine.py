@@ -537,6 +537,33 @@ class RoundPlan:
                                                _lib.ptr(ws), ws.numel()), 'fs_plan_set_krum')
         self._krum = (pick, score, ws)
 
+    def set_rfa(self, on, iters=3, nu=1e-6, init='start', uniform=False, dist=None, b=None, obj=None, ws=None):
+        """fs_plan_set_rfa: RFA on the AGGREGATE phases enqueued from now on -- fs_aggregate_rfa over the
+        round's rows of ``W_out`` with x = ``W_g`` into ``W_g``: ``iters`` smoothed Weiszfeld iterations with
+        the smoothing ``nu`` from ``init`` ('start': ``W_g``; 'mean': the finite rows' weighted mean), under
+        the round's weights or, with ``uniform``, 1 / M.  ``dist`` float64 [N], ``b`` float32 [N] and ``obj``
+        float64 [iters + 2] take every round's distances to the new ``W_g``, last weights (by position) and
+        objectives; ``ws``: ``Aggregator.rfa_ws()`` (uint8).  TRAIN and EVAL are unchanged.  ``on`` false
+        restores the plain aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_rfa(self._h, 0, 0, 0.0, 0, 0, None, None, None, None, 0),
+                       'fs_plan_set_rfa')
+            self._rfa = None
+            return
+        if init not in RFA_INITS:
+            raise ValueError("set_rfa: init must be 'start' or 'mean'")
+        if not (dist is not None and dist.is_cuda and dist.dtype == torch.float64 and dist.is_contiguous()
+                and b is not None and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()
+                and obj is not None and obj.is_cuda and obj.dtype == torch.float64 and obj.is_contiguous()
+                and obj.numel() >= int(iters) + 2
+                and ws is not None and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+            raise ValueError('set_rfa: dist (float64), b (float32), obj (float64 [iters + 2]) and ws (uint8) must be '
+                             'contiguous device tensors')
+        _lib.check(_lib.lib().fs_plan_set_rfa(self._h, 1, int(iters), float(nu), RFA_INITS[init], int(bool(uniform)),
+                                              _lib.ptr(dist), _lib.ptr(b), _lib.ptr(obj), _lib.ptr(ws), ws.numel()),
+                   'fs_plan_set_rfa')
+        self._rfa = (dist, b, obj, ws)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -788,6 +815,45 @@ class Aggregator:
                    'fs_aggregate_krum')
         return out
 
+    def rfa_ws(self, M=None):
+        """A uint8 workspace for ``run_rfa`` at up to ``M`` rows (None: N): fs_aggregate_rfa_ws_bytes, what
+        ``RoundPlan.set_rfa`` asks for."""
+        return torch.empty(max(16, rfa_ws_bytes(self.N if M is None else int(M), self.len)), dtype=torch.uint8,
+                           device=self.ws.device)
+
+    def run_rfa(self, W_all, x, alpha, T, nu, init, out, dist, b, obj, ws, sel=None, check=True):
+        """fs_aggregate_rfa: RFA over the rows ``sel`` of ``W_all`` (None: rows 0..N-1) -- ``T`` smoothed
+        Weiszfeld iterations (smoothing ``nu``) towards their geometric median under the weights ``alpha``
+        (float32 [M]), from ``init`` = 'start' (the round-start model ``x``) or 'mean' (the finite rows'
+        weighted mean), into ``out`` (may be ``x``).  ``dist`` float64 [M]: the distances to ``out``; ``b``
+        float32 [M]: the last weights used; ``obj`` float64 [T + 2]: the smoothed objective at every iterate
+        (NaN in the slots the chain does not reach).  ``ws``: ``rfa_ws()``.  The rule and its orders:
+        include/fedsim.h.  ``check`` as in ``run_sel``."""
+        M = self._krum_rows('run_rfa', W_all, x, sel, False)
+        if M > rfa_max_m():
+            raise ValueError('run_rfa: M = %d is above fs_aggregate_rfa_max_m() = %d' % (M, rfa_max_m()))
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= W_all.numel() // self.len:
+                raise ValueError('run_rfa: sel must index rows of W_all, [0, %d)' % (W_all.numel() // self.len))
+        if init not in RFA_INITS:
+            raise ValueError("run_rfa: init must be 'start' or 'mean'")
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= self.len
+                and alpha.is_cuda and alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.numel() >= M
+                and dist.is_cuda and dist.dtype == torch.float64 and dist.is_contiguous() and dist.numel() >= M
+                and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.numel() >= M
+                and obj.is_cuda and obj.dtype == torch.float64 and obj.is_contiguous()
+                and obj.numel() >= max(0, int(T)) + 2
+                and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+            raise ValueError('run_rfa: out, alpha [M], b [M] (float32), dist [M], obj [T + 2] (float64) and ws (uint8) '
+                             'must be contiguous device tensors')
+        _lib.check(_lib.lib().fs_aggregate_rfa(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                               self.len, _lib.ptr(x), _lib.ptr(alpha), int(T), float(nu),
+                                               RFA_INITS[init], _lib.ptr(out), _lib.ptr(dist), _lib.ptr(b),
+                                               _lib.ptr(obj), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   'fs_aggregate_rfa')
+        return out
+
     def run_robust(self, W_all, b, out, sel=None, check=True):
         """fs_aggregate_robust: the coordinate-wise trimmed mean of the rows ``sel`` of ``W_all`` (None:
         rows 0..N-1) with the trim count ``b``, 0 <= 2b < M: per coordinate the b smallest and the b
@@ -814,6 +880,72 @@ class Aggregator:
                                                   self.len, int(b), _lib.ptr(out), _lib.stream_ptr()),
                    'fs_aggregate_robust')
         return out
+
+
+RFA_INITS = {'start': 0, 'mean': 1}      # FS_RFA_INIT_*
+
+
+def rfa_max_m():
+    """fs_aggregate_rfa_max_m: the largest number of rows ``Aggregator.run_rfa`` accepts."""
+    return int(_lib.lib().fs_aggregate_rfa_max_m())
+
+
+def rfa_width(M):
+    """fs_rfa_width: the columns of a stripe of fs_rfa_step at M rows (32, 16 or 8) -- it fixes the
+    summation orders (include/fedsim.h)."""
+    return int(_lib.lib().fs_rfa_width(int(M)))
+
+
+def rfa_ws_bytes(M, length):
+    """fs_aggregate_rfa_ws_bytes: the bytes of workspace fs_aggregate_rfa needs at up to M rows of
+    ``length`` floats."""
+    return int(_lib.lib().fs_aggregate_rfa_ws_bytes(int(M), int(length)))
+
+
+def rfa_step(W_all, length, v, b, flag, v_out, part, sel=None, M=None):
+    """fs_rfa_step: one iteration from one read of the rows ``sel`` of ``W_all`` (None: rows 0..M-1), each of
+    ``length`` floats.  ``b`` / ``flag`` None: pass 0 (``v_out`` = ``v``); else ``v_out`` = the fold with the
+    weights ``b`` float32 [M] (``flag`` int32 [1] non-zero: ``v`` instead).  ``part`` float64
+    [ceil(length / rfa_width(M)), M] takes every row's partial squared distance to ``v_out`` per stripe."""
+    M = int(sel.numel()) if sel is not None else int(M)
+    W = max(1, rfa_width(M))
+    for name, t, dt, n in (('W_all', W_all, torch.float32, 1 if sel is not None else M * int(length)),
+                           ('v', v, torch.float32, int(length)), ('v_out', v_out, torch.float32, int(length)),
+                           ('part', part, torch.float64, -(-int(length) // W) * M)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
+            raise ValueError('rfa_step: %s must be a contiguous %s device tensor of at least %d elements' % (name, dt, n))
+    if (b is None) != (flag is None):
+        raise ValueError('rfa_step: b and flag come together')
+    if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.numel() >= M
+                              and flag.is_cuda and flag.dtype == torch.int32 and flag.numel() >= 1):
+        raise ValueError('rfa_step: b (float32 [M]) and flag (int32 [1]) must be contiguous device tensors')
+    if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous()):
+        raise ValueError('rfa_step: sel must be a contiguous int32 device tensor')
+    _lib.check(_lib.lib().fs_rfa_step(_lib.ptr(W_all), int(length), None if sel is None else _lib.ptr(sel), M,
+                                      int(length), _lib.ptr(v), None if b is None else _lib.ptr(b),
+                                      None if flag is None else _lib.ptr(flag), _lib.ptr(v_out), _lib.ptr(part),
+                                      _lib.stream_ptr()), 'fs_rfa_step')
+    return v_out, part
+
+
+def rfa_weights(part, M, length, alpha, nu, d2, dist, b, obj, flag, mean=False):
+    """fs_rfa_weights: ``part`` (``rfa_step``'s table; None: ``d2`` as given) reduced into ``d2`` float64 [M],
+    then ``dist`` float64 [M], the weights ``b`` float32 [M], the objective ``obj`` float64 [1] and ``flag``
+    int32 [1] (1: no finite row) under ``alpha`` float32 [M] and ``nu``; ``mean``: the weighted-mean weights."""
+    M = int(M)
+    for name, t, dt, n in (('alpha', alpha, torch.float32, M), ('d2', d2, torch.float64, M),
+                           ('dist', dist, torch.float64, M), ('b', b, torch.float32, M),
+                           ('obj', obj, torch.float64, 1), ('flag', flag, torch.int32, 1)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
+            raise ValueError('rfa_weights: %s must be a contiguous %s device tensor of at least %d elements'
+                             % (name, dt, n))
+    if part is not None and not (part.is_cuda and part.dtype == torch.float64 and part.is_contiguous()
+                                 and part.numel() >= -(-int(length) // max(1, rfa_width(M))) * M):
+        raise ValueError('rfa_weights: part must be a contiguous float64 device tensor [stripes, M]')
+    _lib.check(_lib.lib().fs_rfa_weights(None if part is None else _lib.ptr(part), M, int(length), _lib.ptr(alpha),
+                                         float(nu), int(bool(mean)), _lib.ptr(d2), _lib.ptr(dist), _lib.ptr(b),
+                                         _lib.ptr(obj), _lib.ptr(flag), _lib.stream_ptr()), 'fs_rfa_weights')
+    return b
 
 
 def krum_max_m():

@@ -62,6 +62,8 @@ EXTRA_FAIR = ['QFedAvg']
 EXTRA_ROBUST = ['FedMedian', 'FedTrimmedMean']
 # Krum and Multi-Krum (not in the reference) after the robust rows, in this order; once more a list of its own
 EXTRA_KRUM = ['Krum', 'MultiKrum']
+# RFA, the geometric median (not in the reference) after the Krum rows; a list of its own as well
+EXTRA_RFA = ['FedRFA']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -101,16 +103,16 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
         algos=tuple(NAMES), synth=None, verbose=True, client_eval=None, local_eval=None, participation=None,
         sample_seed=0, server_lr=None, server_beta1=0.9, server_beta2=0.99, server_tau=1e-3, qffl_q=1.0,
         qffl_weighting='size', robust_trim=0.1, byzantine_fraction=0.0, byzantine_attack='sign_flip',
-        byzantine_scale=1.0, krum_f=0.1):
+        byzantine_scale=1.0, krum_f=0.1, rfa_iters=3, rfa_nu=1e-6, rfa_init='start', rfa_weighting='size'):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
         raise ValueError("local_eval must be None, 'global', 'own' or 'both'")
-    known = NAMES + EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM
+    known = NAMES + EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM + EXTRA_RFA
     unknown = [n for n in algos if n not in known]
     if unknown:
         raise ValueError('unknown algorithm(s) %s (known: %s)' % (', '.join(unknown), ', '.join(known)))
-    names = list(NAMES) + [n for n in EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM if n in algos]
+    names = list(NAMES) + [n for n in EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM + EXTRA_RFA if n in algos]
     lwant = {None: (), 'both': ('global', 'own')}.get(local_eval, (local_eval,))
     want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
     cev = {'client_%s_%s' % (w, m): [None] * len(names) for w in want for m in ('loss', 'acc')}
@@ -296,6 +298,24 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             keep_participants(name, st)
             k = names.index(name)
             train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        for name in EXTRA_RFA:
+            if name not in algos:
+                continue
+            # FedAvg's arguments; clients are always parallel.  The --rfa-* flags, and the --byzantine-*
+            # flags as for the robust and Krum rows
+            st = ce(name, False)
+            if participation is not None:
+                st = st or {}
+            rpar = dict(kw) if participation is None else dict(participation=participation, sample_seed=sample_seed,
+                                                               **kw)
+            rpar.update(iters=rfa_iters, nu=rfa_nu, init=rfa_init, weighting=rfa_weighting)
+            if byzantine_fraction > 0:
+                rpar['byzantine'] = dict(fraction=byzantine_fraction, attack=byzantine_attack, scale=byzantine_scale)
+            r = timed(name, lambda: getattr(tools, name)(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False,
+                                                         0, Round, stats=st, **rpar))
+            keep_participants(name, st)
+            k = names.index(name)
+            train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -329,7 +349,7 @@ def main(argv=None):
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES),
                     help='comma-separated; FedNova (exp.py:124, commented out there), Scaffold, FedAvgM, FedAdagrad, '
-                         'FedAdam, FedYogi, QFedAvg, FedMedian, FedTrimmedMean, Krum and MultiKrum run only when named here')
+                         'FedAdam, FedYogi, QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum and FedRFA run only when named here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -338,7 +358,7 @@ def main(argv=None):
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
                          'Applies to the FedAvg, FedProx, FedNova, Scaffold, server-optimizer (FedAvgM, FedAdagrad, '
-                         'FedAdam, FedYogi), QFedAvg, FedMedian, FedTrimmedMean, Krum and MultiKrum calls only, which then run with parallel clients '
+                         'FedAdam, FedYogi), QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum and FedRFA calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')
@@ -354,8 +374,16 @@ def main(argv=None):
                     help='FedTrimmedMean: the fraction trimmed per side, in [0, 0.5)')
     ap.add_argument('--krum-f', type=float, default=0.1, metavar='F',
                     help='Krum, MultiKrum: the fraction of the clients that may misbehave, in [0, 0.5)')
+    ap.add_argument('--rfa-iters', type=int, default=3, metavar='T',
+                    help='FedRFA: the smoothed Weiszfeld iterations per round, in [0, 32]')
+    ap.add_argument('--rfa-nu', type=float, default=1e-6, help='FedRFA: the smoothing nu > 0')
+    ap.add_argument('--rfa-init', default='start', choices=['start', 'mean'],
+                    help="FedRFA: iterate from the round-start model, or from the weighted mean as the paper does "
+                         "(no robustness claim at few iterations)")
+    ap.add_argument('--rfa-weighting', default='size', choices=['size', 'uniform'],
+                    help='FedRFA: the client weights p_k, n_k / n or 1 / M')
     ap.add_argument('--byzantine-fraction', type=float, default=0.0, metavar='F',
-                    help='FedMedian, FedTrimmedMean, Krum, MultiKrum: the share of the clients that misbehave (0: none)')
+                    help='FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA: the share of the clients that misbehave (0: none)')
     ap.add_argument('--byzantine-attack', default='sign_flip', choices=['sign_flip', 'gaussian', 'nan'],
                     help='what the misbehaving clients return')
     ap.add_argument('--byzantine-scale', type=float, default=1.0, help='the scale of sign_flip and gaussian')
@@ -366,7 +394,8 @@ def main(argv=None):
               server_lr=a.server_lr, server_beta1=a.server_beta1, server_beta2=a.server_beta2,
               server_tau=a.server_tau, qffl_q=a.qffl_q, qffl_weighting=a.qffl_weighting,
               robust_trim=a.robust_trim, byzantine_fraction=a.byzantine_fraction, byzantine_attack=a.byzantine_attack,
-              byzantine_scale=a.byzantine_scale, krum_f=a.krum_f)
+              byzantine_scale=a.byzantine_scale, krum_f=a.krum_f, rfa_iters=a.rfa_iters, rfa_nu=a.rfa_nu,
+              rfa_init=a.rfa_init, rfa_weighting=a.rfa_weighting)
     for k, name in enumerate(out['name']):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

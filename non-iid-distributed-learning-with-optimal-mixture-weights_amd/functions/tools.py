@@ -487,6 +487,35 @@ def _check_krum_rounds(Ms, f, m, max_m):
     return out
 
 
+RFA_INITS = ('start', 'mean')
+RFA_MAX_ITERS = 32
+
+
+def _check_rfa(iters, nu, init, weighting, clients='parallel'):
+    """FedRFA's keyword checks (host only: before any device is touched)."""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= iters <= RFA_MAX_ITERS:
+        raise ValueError('iters must be an int count in [0, %d]' % RFA_MAX_ITERS)
+    if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)) \
+            or not (float(nu) > 0.0 and math.isfinite(float(nu))):
+        raise ValueError('nu must be a positive, finite number')
+    if init not in RFA_INITS:
+        raise ValueError("init must be 'start' or 'mean'")
+    if weighting not in SCAFFOLD_WEIGHTINGS:
+        raise ValueError("weighting must be 'size' or 'uniform'")
+    if clients != 'parallel':
+        raise ValueError("FedRFA needs clients='parallel': a chained client's row holds its predecessors' work")
+
+
+def _check_rfa_rounds(Ms, max_m):
+    """ValueError for a round with no client or above ``max_m`` clients."""
+    for t, M in enumerate(Ms):
+        if M < 1:
+            raise ValueError('FedRFA: round %d has no client' % t)
+        if M > max_m:
+            raise ValueError('FedRFA: round %d has M = %d clients, above fs_aggregate_rfa_max_m() = %d'
+                             % (t, M, max_m))
+
+
 def byzantine_plan(N, byzantine):
     """``byzantine=`` checked and resolved (host only): None, or (sorted int64 ids, attack, scale, seed).
     ``ids``: the client ids given; ``fraction``: floor(fraction * N) ids fixed once from ``seed``
@@ -531,9 +560,17 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None):
+                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None, rfa=None):
         self.robust = algo == 'fedrobust'
         self.byz = None
+        self.rfa = algo == 'fedrfa'
+        if self.rfa:
+            # rfa: dict(iters=, nu=, init=, byzantine=) (tools.FedRFA); weighting is the keyword above
+            rf = dict(rfa or {})
+            self.rf_T, self.rf_nu, self.rf_init = rf.get('iters', 3), rf.get('nu', 1e-6), rf.get('init', 'start')
+            _check_rfa(self.rf_T, self.rf_nu, self.rf_init, weighting, clients)
+            self.rf_uniform = weighting == 'uniform'
+            self.byz = byzantine_plan(len(y_train), rf.get('byzantine'))
         self.krum = algo == 'fedkrum'
         if self.krum:
             # krum: dict(f=, m=, byzantine=) (tools.FedKrum)
@@ -595,7 +632,8 @@ class Federation:
         # (None: every client, every round -- the code path without the keyword, untouched)
         self.sched = None
         if participation is not None:
-            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust', 'fedkrum'):
+            if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust', 'fedkrum',
+                            'fedrfa'):
                 raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
                                           'FedOpt, QFedAvg and FedRobust only')
             if self.chained:
@@ -627,6 +665,12 @@ class Federation:
                 raise NotImplementedError('FedKrum over more than one torch.distributed rank is not implemented')
             self.kr_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
             self.kr_fm = _check_krum_rounds(self.kr_M, self.kr_f, self.kr_m, engine.krum_max_m())
+        if self.rfa:
+            if nranks > 1:
+                # (the distances need all clients' rows)
+                raise NotImplementedError('FedRFA over more than one torch.distributed rank is not implemented')
+            self.rf_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
+            _check_rfa_rounds(self.rf_M, engine.rfa_max_m())
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -841,6 +885,13 @@ class Federation:
             self.kr_pick = torch.full((R, self.N), -1, dtype=torch.int32, device=dev)
             self.kr_score = torch.full((R, self.N), float('nan'), dtype=torch.float64, device=dev)
             self.kr_ws = self.agg.krum_ws()
+        if self.rfa:
+            # FedAvg's round with fs_aggregate_rfa as its aggregate; every round's weights, distances and
+            # objectives land in that round's row of the histories (the setter is called again before each round)
+            self.rf_b = torch.full((R, self.N), float('nan'), dtype=torch.float32, device=dev)
+            self.rf_dist = torch.full((R, self.N), float('nan'), dtype=torch.float64, device=dev)
+            self.rf_obj = torch.full((R, int(self.rf_T) + 2), float('nan'), dtype=torch.float64, device=dev)
+            self.rf_ws = self.agg.rfa_ws()
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -922,6 +973,9 @@ class Federation:
             # (f + 1/2) / M: the fraction whose floor(. * M) is this round's f inside the plan
             f_t, m_t = self.kr_fm[t]
             self.plan.set_krum(True, (f_t + 0.5) / self.kr_M[t], m_t, self.kr_pick[t], self.kr_score[t], self.kr_ws)
+        if self.rfa:
+            self.plan.set_rfa(True, self.rf_T, self.rf_nu, self.rf_init, self.rf_uniform, self.rf_dist[t],
+                              self.rf_b[t], self.rf_obj[t], self.rf_ws)
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -1111,6 +1165,16 @@ class Federation:
                     S = np.arange(self.N) if self.sched is None else self.sched[t]
                     scores[t, S] = sh[t, :len(S)]
                 self.stats['krum_scores'] = scores
+                if self.byz is not None:
+                    self.stats['byzantine_ids'] = self.byz[0].copy()
+            if self.rfa:
+                bh, dh = self.rf_b[:R].cpu().numpy().astype(np.float64), self.rf_dist[:R].cpu().numpy()
+                wts, dst = np.full((R, self.N), np.nan), np.full((R, self.N), np.nan)
+                for t in range(R):
+                    S = np.arange(self.N) if self.sched is None else self.sched[t]
+                    wts[t, S], dst[t, S] = bh[t, :len(S)], dh[t, :len(S)]
+                self.stats['rfa_weights'], self.stats['rfa_dist'] = wts, dst
+                self.stats['rfa_objective'] = self.rf_obj[:R].cpu().numpy()
                 if self.byz is not None:
                     self.stats['byzantine_ids'] = self.byz[0].copy()
             if self.mixture is not None:
@@ -1376,6 +1440,33 @@ def MultiKrum(X_train, y_train, X_test, y_test, type='classification', num_class
     return FedKrum(X_train, y_train, X_test, y_test, type, num_classes, D, lr, epoch, batch_size, prox, mu,
                    lambda_reg_if, lambda_reg, round, f=f, m=None, byzantine=byzantine, stats=stats, verbose=verbose,
                    options=options, participation=participation, sample_seed=sample_seed)
+
+
+def FedRFA(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+           batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, iters=3, nu=1e-6,
+           init='start', weighting='size', byzantine=None, stats=None, verbose=True, options=None, participation=None,
+           sample_seed=0):
+    """RFA (Pillutla, Kakade, Harchaoui, IEEE TSP 2022; not in the reference): FedAvg's positional list,
+    clients always parallel.  Local training is FedAvg's launch unchanged -- both tasks, ``prox=True``, any
+    ``batch_size`` the task's trainer accepts, ``participation`` -- and the server step is fs_aggregate_rfa:
+    ``iters`` smoothed Weiszfeld iterations towards the geometric median of the round's M models under the
+    weights p_k (``weighting='size'``: the round's FedAvg weights; ``'uniform'``: 1 / M), each one distance
+    pass and one fold with the weights p_k / max(nu, ||W_k - v||); a row that is not finite weighs 0.
+    ``init='start'`` iterates from the round-start model, ``'mean'`` from the finite rows' weighted mean as
+    the paper does -- which one finite row of huge norm drags far out at small ``iters``: it is offered for
+    fidelity and carries no robustness claim.  ``byzantine=`` as in ``FedRobust``.  The global generator is
+    consumed exactly as by ``FedAvg(clients='parallel')`` with the same ``participation``, and ``train_loss``
+    is FedAvg's.  ``stats['rfa_weights']`` [R, N] float64 (the last weights used; NaN where a client was not
+    sampled), ``stats['rfa_dist']`` [R, N] (the distances to the new global model), ``stats['rfa_objective']``
+    [R, iters + 2] and ``stats['byzantine_ids']``.  ValueError for a bad ``iters``, ``nu``, ``init``,
+    ``weighting`` or ``byzantine``, or a round with M = 0 or M above ``engine.rfa_max_m()``;
+    NotImplementedError over more than one torch.distributed rank."""
+    _check_rfa(iters, nu, init, weighting)
+    byzantine_plan(len(y_train), byzantine)
+    return _run('fedrfa', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed, weighting=weighting,
+                rfa=dict(iters=iters, nu=nu, init=init, byzantine=byzantine))
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
