@@ -10,8 +10,9 @@
 //   x'    = fl(x + fl(coef * S))
 //
 // The fold is aggregate_opt.hip's, term for term and regime for regime (one_launch_sub,
-// aggregate_chunks, AG_FP_SUB, the stage-2 tree of aggregate_sel.h; the first term of a range is
-// the term itself), so S is bitwise fs_aggregate_opt's delta.  Its load schedule too: one float4 of
+// aggregate_chunks, AG_FP_SUB of aggregate_geom.h, the stage-2 tree of aggregate_fold.h; the first
+// term of a range is the term itself), so S is bitwise fs_aggregate_opt's delta.  The kernels stay
+// this file's own: the range fold runs the wave in lockstep and writes the norm table.  Its load schedule too: one float4 of
 // the len parameters per thread, 8 row loads in flight, the next group's row indices loaded behind
 // them, no load under a condition (a short last group loads clamped and skips its folds and its
 // norm terms).
@@ -42,9 +43,8 @@
 //
 // fs_qffl_coef: the round's coefficients u_k = p_k Ft^q, g_k = p_k q Ft^(q-1) L^2 from the losses
 // fs_eval_clients left on the device, in double, rounded once.
+#include "aggregate_fold.h"
 #include "aggregate_sel.h"
-#include "common.h"
-#include "finalize.h"
 #include "lanes.h"
 
 namespace fs {
@@ -57,15 +57,7 @@ struct QfCoef {
   const float* u;       // [M]
 };
 
-// (a template parameter, not a test of the pointer: see aggregate_nova.hip)
-template <bool SEL>
-__device__ __forceinline__ int qf_row(const int32_t* __restrict__ sel, int k) { return SEL ? sel[k] : k; }
-
-__device__ __forceinline__ float4 qadd4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-
-// One group of up to 8 terms k .. k+7 (< k1) folded onto acc, opt_fold_group's schedule; e[u] is
+// One group of up to 8 terms k .. k+7 (< k1) folded onto acc, aggregate_fold.h's fold_group schedule; e[u] is
 // the thread's norm term of row k + u (left as it is where the row does not exist).
 template <bool SEL, bool FULL>
 __device__ __forceinline__ float4 qf_fold_group(const float* __restrict__ W, int64_t stride, const QfCoef& c, float4 x,
@@ -80,7 +72,7 @@ __device__ __forceinline__ float4 qf_fold_group(const float* __restrict__ W, int
     uv[u] = c.u[ku];
   }
 #pragma unroll
-  for (int u = 0; u < 8; ++u) idx[u] = qf_row<SEL>(c.sel, min(k + 8 + u, last));
+  for (int u = 0; u < 8; ++u) idx[u] = fold_row<SEL>(c.sel, min(k + 8 + u, last));
   if (!FULL) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) asm volatile("" : "+v"(uv[u]));
@@ -95,7 +87,7 @@ __device__ __forceinline__ float4 qf_fold_group(const float* __restrict__ W, int
       if (u == 0 && k == k0)
         acc = t;
       else
-        acc = qadd4(acc, t);
+        acc = add4(acc, t);
     }
   return acc;
 }
@@ -137,7 +129,7 @@ __device__ __forceinline__ float4 qf_fold_range(const float* __restrict__ W, int
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int idx[8];
 #pragma unroll
-  for (int u = 0; u < 8; ++u) idx[u] = k0 < k1 ? qf_row<SEL>(c.sel, min(k0 + u, k1 - 1)) : 0;
+  for (int u = 0; u < 8; ++u) idx[u] = k0 < k1 ? fold_row<SEL>(c.sel, min(k0 + u, k1 - 1)) : 0;
   for (int g = 0; g < groups; ++g) {
     const int k = k0 + 8 * g;
     float e[8];
@@ -160,7 +152,7 @@ __device__ __forceinline__ float4 qf_fold_range(const float* __restrict__ W, int
   return acc;
 }
 
-// two-stage form, stage 1 (aggregate_opt_kernel's geometry): chunk blockIdx.y folds k in
+// two-stage form, stage 1 (fold_chunk_kernel's geometry): chunk blockIdx.y folds k in
 // [y * per, min(M, y * per + per)) into partial y; FINAL (one chunk): straight into S.  Column of
 // the table: 4 * blockIdx.x + wave.
 template <bool SEL, bool FINAL>
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(256) void aggregate_qffl_kernel(const float* __rest
   if (live) st4(out + (FINAL ? 0 : (int64_t)ch * 4 * len4) + 4 * i, acc);
 }
 
-// one-launch form (aggregate_opt_one_kernel's geometry): SUB consecutive ranges of k per float4
+// one-launch form (fold_one_kernel's geometry): SUB consecutive ranges of k per float4
 // position folded by SUB threads of one workgroup, their partials folded in order in LDS; the
 // deferred evaluation's finaliser rides as the last workgroup.  Column of the table:
 // blockIdx.x * (POS / LANES) + the segment's place among the sub-range's positions.
@@ -209,7 +201,7 @@ __global__ __launch_bounds__(256) void aggregate_qffl_one_kernel(const float* __
   __syncthreads();
   if (sub == 0 && live) {
     float4 t = sums[0][pl];
-    for (int s2 = 1; s2 < SUB && s2 * per < M; ++s2) t = qadd4(t, sums[s2][pl]);
+    for (int s2 = 1; s2 < SUB && s2 * per < M; ++s2) t = add4(t, sums[s2][pl]);
     st4(S + 4 * i, t);
   }
 }

@@ -1,20 +1,14 @@
-// What fs_aggregate (aggregate.hip), fs_aggregate_sel (aggregate_sel.hip) and fs_aggregate_nova
-// (aggregate_nova.hip) share: the regime
-// threshold, the sub-range and chunk rules and the stage-2 fold, so the gathered fold takes the
-// same path as the contiguous one at the same client count -- its contract is bitwise equality.
+// The aggregation rules' launchers, as the round plan (round.hip) and each other call them.  The
+// regime threshold and the sub-range and chunk rules they share are aggregate_geom.h's, the kernels
+// and the dispatch of the weighted folds aggregate_fold.h's.
 #pragma once
+#include "aggregate_geom.h"
 #include "finalize.h"
 
 namespace fs {
 
-constexpr int AG_ONE_MAX_N = 512;   // clients up to which chunks <= 0 is the one-launch form
-constexpr int AG_FP_SUB = 8;        // threads per float4 position of the stage-2 tree (fold_partials_launch)
-
-int one_launch_sub(int N);          // sub-ranges per float4 position of the one-launch form
-// chunks and clients per chunk of the two-stage form (chunks <= 0: by the shape; clamped to the
-// partials the workspace holds)
-int aggregate_chunks(int N, int chunks, bool has_ws, int64_t ws_floats, int64_t len, int* per_out);
-// stage 2: K partials of 4 * len4 floats at d_part folded by the fixed tree into d_out
+// stage 2 of a plain sum (aggregate.hip): K partials of 4 * len4 floats at d_part folded by the fixed
+// tree into d_out
 void fold_partials_launch(const float* d_part, int K, int64_t len4, float* d_out, hipStream_t st);
 
 // fs_aggregate_sel with an optional finaliser (nullptr: none), as aggregate_launch

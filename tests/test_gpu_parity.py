@@ -512,7 +512,7 @@ def test_aggregate_auto_forms(amd, N):
     the N products' fp32 sum differs, so each element lies within the classical bound of two
     recursive summations of the same terms, 2 (N - 1) u sum_j |p_j W_j| (u = 2^-24), of the
     reference's fold.  17 / 47 / 48 / 95 / 96 / 97 are the steps of one_launch_sub (2, 4, 8 and
-    16 sub-ranges per position; 48 to 95 clients are the only ones on aggregate_one_kernel<8>)."""
+    16 sub-ranges per position; 48 to 95 clients are the only ones on fold_one_kernel<PlainRule, 8>)."""
     rs = np.random.RandomState(N)
     C, D = 10, 2048
     Ws = rs.normal(size=(N, C, D)).astype(np.float32)
