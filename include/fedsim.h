@@ -660,6 +660,60 @@ int fs_aggregate_rfa(const float* d_W_all, int64_t stride, const int32_t* d_sel,
                      float* d_b, double* d_obj, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * FedTopK: top-k sparsified uploads with error feedback (Aji & Heafield, EMNLP 2017; Stich,
+ * Cordonnier & Jaggi, NeurIPS 2018; Sattler et al. 2019).  Additive to ABI 23: the entry points
+ * below, FS_ABI_VERSION unchanged.
+ *
+ * The rule, over the round's M rows W_k (k the position in d_sel, NULL: rows 0..M-1) of d_W_all,
+ * each of len floats, x = d_W_g [len] on entry, the residual rows e_k of d_e ([clients][stride]
+ * floats, indexed by client id as d_W_all; NULL: no memory), the weights q_k (d_q [M]) and a count
+ * 1 <= kcount <= len; all arithmetic is IEEE, every operation rounded separately, nothing contracted.
+ *   Update.    a_k[i] = fl(fl(W_k[i] - x[i]) + e_k[i]); without memory a_k[i] = fl(W_k[i] - x[i]).
+ *   Threshold. key(v) = bits(v) & 0x7fffffff as uint32: magnitude order, the sign ignored, Inf above
+ *     every finite value and NaN above Inf.  tau_k = the kcount-th largest of the row's len keys.
+ *     Position i is kept iff key(a_k[i]) >= tau_k: ties at the threshold are all kept, so the kept
+ *     count n_k >= kcount, and an all-zero row keeps everything.  Integer selection: exact,
+ *     order-independent, the same bits on every run.  A NaN or an Inf is therefore always
+ *     transmitted: the rule carries no robustness claim.
+ *   Residual.  e_k[i] <- kept ? +0.0f : a_k[i], in place.  Rows of clients outside d_sel are neither
+ *     read nor written; without memory nothing is stored.
+ *   Fold.      s_k[i] = kept ? a_k[i] : +0.0f, d_W_g[i] <- fl(x[i] + sum_k fl(q_k * s_k[i])), k
+ *     ascending, folded exactly as fs_aggregate_nova folds FS_NOVA_UPDATES before it adds its base:
+ *     the first term of a range the term itself; regimes, sub-ranges, chunks and the stage-2 tree
+ *     fs_aggregate's, chosen by M and `chunks`, d_ws / ws_floats one partial per chunk.
+ *   Outputs.   d_tau[k]: a float whose bits are the key tau_k.  d_kept[k] = n_k (int32).
+ * Dense identity: with kcount == len -- or any kcount at which every nonzero is kept -- and e == 0
+ * on entry, d_W_g is bitwise what fs_aggregate_opt(FS_OPT_AVGM, beta1 = 0, eta = 1) leaves with the
+ * same q, chunks and workspace, and e stays all +0 -- for rows without negative-zero differences
+ * (fl(W_k[i] - x[i]) = -0 becomes +0 when e_k[i] = +0 is added; the identity needs a memory-free call,
+ * d_e == NULL, to hold there as well).
+ *
+ * fs_topk_threshold: stage A, one workgroup per row.  With memory it LEAVES a_k IN e_k (the residual
+ * is completed by the fold) and writes d_tau and d_kept; without, d_tau and d_kept only.  Reads
+ * 2 M len floats (W_k, e_k; x from cache) and writes M len, then reads a_k back three times (a row
+ * just written: cache hits); without memory 4 reads of W_k.  A radix select on the keys, most
+ * significant digit first (8, 8, 8, 7 bits), the counts in LDS integer atomics.  d_ws / ws_bytes:
+ * fs_aggregate_topk_ws_bytes(M, len) bytes, which is 0 (d_ws may be NULL).
+ * fs_aggregate_topk: stage A, then the thresholded fold (1 or 2 launches, as fs_aggregate_nova),
+ * which reads M len floats (a_k from d_e; without memory W_k, and x per sub-range), stores zeros
+ * over the float4s of e_k that hold a kept position, and writes len floats of d_W_g.  d_sws /
+ * sws_bytes as d_ws / ws_bytes above.  d_W_g is updated in place.
+ * No float atomics, no global atomics, no cross-workgroup wait, no allocation, no host
+ * synchronisation; the same bits on every call and for the same rows gathered from a larger buffer.
+ * tests/topk_restatement.py restates the rule in numpy; the kernels equal it bit for bit.
+ * FS_EINVAL, and nothing is written then, for M < 1, kcount < 1 or kcount > len, len or stride no
+ * multiple of 4, stride < len, len >= 2^31, a null pointer (d_sel, d_e, d_ws and d_sws may be NULL),
+ * a workspace that is too small, or d_e equal to d_W_all or d_W_g.
+ * ------------------------------------------------------------------------- */
+int64_t fs_aggregate_topk_ws_bytes(int M, int64_t len);
+int fs_topk_threshold(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len,
+                      const float* d_W_g, float* d_e, int64_t kcount, float* d_tau, int32_t* d_kept, void* d_ws,
+                      int64_t ws_bytes, void* stream);
+int fs_aggregate_topk(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
+                      int64_t len, int64_t kcount, float* d_W_g, float* d_e, float* d_tau, int32_t* d_kept,
+                      float* d_ws, int64_t ws_floats, int chunks, void* d_sws, int64_t sws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -1151,6 +1205,24 @@ int fs_plan_set_krum(fs_plan* plan, int on, double f_frac, int m_mode, int32_t* 
  * fs_plan_set_qffl, fs_plan_set_robust and fs_plan_set_krum refuse in turn while it is on. */
 int fs_plan_set_rfa(fs_plan* plan, int on, int T, double nu, int init, int uniform, double* d_dist, float* d_b,
                     double* d_obj, void* d_ws, int64_t ws_bytes);
+
+/* (additive to ABI 23) FedTopK on this plan's AGGREGATE phase.  Host state read when the next round
+ * call enqueues, as fs_plan_set_rfa's.  on = 1: AGGREGATE launches fs_aggregate_topk over the
+ * round's rows of d_W_out (all N, or the subset call's M ids) with the round's normalised weights
+ * as q (d_p_override or the plan's p, the subset call's q), kcount as given, d_W_g in place, the
+ * plan's aggregation workspace and chunks, and the pending finaliser of a deferred evaluation on
+ * the fold.  d_e [N][C * ld] floats is the clients' residual memory, updated in place by client id
+ * (a client outside the round keeps its row); NULL: top-k without memory.  d_tau [N] float and
+ * d_kept [N] int32 take the round's thresholds and kept counts (by position); d_sws of sws_bytes >=
+ * fs_aggregate_topk_ws_bytes(N, C * ld) bytes (0: may be NULL).  TRAIN and EVAL are unchanged: every
+ * training form, the prox term, loss = 1, B > 64 and subset rounds work as without it.  on = 0
+ * restores the plain aggregate.  FS_EINVAL for a chained plan, kcount outside [1, C * ld], a null
+ * d_tau or d_kept, d_e equal to d_W_g or d_W_out, a workspace that is too small, a nova mode other
+ * than 0, SCAFFOLD on, a server-optimizer rule set, q-FedAvg on, a robust aggregate on, Krum on or
+ * RFA on; fs_plan_set_nova, fs_plan_set_scaffold, fs_plan_set_server_opt, fs_plan_set_qffl,
+ * fs_plan_set_robust, fs_plan_set_krum and fs_plan_set_rfa refuse in turn while it is on. */
+int fs_plan_set_topk(fs_plan* plan, int on, int64_t kcount, float* d_e, float* d_tau, int32_t* d_kept, void* d_sws,
+                     int64_t sws_bytes);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

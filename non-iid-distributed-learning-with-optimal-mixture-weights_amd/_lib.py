@@ -97,6 +97,15 @@ _SIGS = {
                                    C.c_void_p, C.c_int64, C.c_void_p]),
     'fs_plan_set_rfa': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int64]),
+    # FedTopK, top-k sparsified uploads with error feedback (additive to ABI 23)
+    'fs_aggregate_topk_ws_bytes': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_topk_threshold': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_aggregate_topk': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_plan_set_topk': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -396,6 +405,8 @@ KERNEL_SOURCES = {
     'aggregate_robust': ('aggregate_robust.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_krum': ('aggregate_krum.hip', 'aggregate_sel.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_rfa': ('aggregate_rfa.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
+    'aggregate_topk': ('aggregate_topk.hip', 'aggregate_fold.h', 'aggregate_geom.h', 'aggregate_sel.h', 'finalize.h',
+                       'common.h'),
 }
 
 

@@ -56,4 +56,11 @@ int aggregate_rfa_launch(const float* d_W_all, int64_t stride, const int32_t* d_
                          const EvalFinalize* fin, hipStream_t st);
 int64_t aggregate_rfa_ws_bytes(int M, int64_t len);
 
+// fs_aggregate_topk (aggregate_topk.hip) with an optional finaliser, which rides on the thresholded fold
+int aggregate_topk_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
+                          int64_t len, int64_t kcount, float* d_W_g, float* d_e, float* d_tau, int32_t* d_kept,
+                          float* d_ws, int64_t ws_floats, int chunks, void* d_sws, int64_t sws_bytes,
+                          const EvalFinalize* fin, hipStream_t st);
+int64_t aggregate_topk_ws_bytes(int M, int64_t len);
+
 }  // namespace fs

@@ -54,6 +54,11 @@
 // RFA (additive to ABI 23, fs_plan_set_rfa): AGGREGATE launches fs_aggregate_rfa (aggregate_rfa.hip),
 // T smoothed Weiszfeld iterations over the round's rows from x = d_W_g into d_W_g, under the
 // round's weights or uniform ones.  TRAIN is untouched, and the finaliser rides on the last step.
+//
+// FedTopK (additive to ABI 23, fs_plan_set_topk): AGGREGATE launches fs_aggregate_topk
+// (aggregate_topk.hip), the per-row top-k threshold of the round's corrected updates and their
+// thresholded fold onto d_W_g, the clients' residuals updated in place.  TRAIN is untouched, and the
+// finaliser rides on the fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -233,6 +238,14 @@ struct fs_plan {
   double* rf_obj = nullptr;           // [T + 2]
   void* rf_ws = nullptr;
   int64_t rf_ws_bytes = 0;
+  // fs_plan_set_topk: AGGREGATE is fs_aggregate_topk
+  int topk = 0;
+  int64_t tk_count = 0;
+  float* tk_e = nullptr;              // [N][C][ld] residuals (nullptr: no memory)
+  float* tk_tau = nullptr;            // [N]
+  int32_t* tk_kept = nullptr;         // [N]
+  void* tk_ws = nullptr;
+  int64_t tk_ws_bytes = 0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -901,6 +914,10 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       rc = fs::aggregate_rfa_launch(d.d_W_out, len, sel, M, len, d.d_W_g, p->rf_uniform ? nullptr : pw,
                                     (float)(1.0 / (double)M), p->rf_T, p->rf_nu, p->rf_init, d.d_W_g, p->rf_dist,
                                     p->rf_b, p->rf_obj, p->rf_ws, p->rf_ws_bytes, f, st);
+    } else if (p->topk) {
+      rc = fs::aggregate_topk_launch(d.d_W_out, len, sel, pw, M, len, p->tk_count, d.d_W_g, p->tk_e, p->tk_tau,
+                                     p->tk_kept, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, p->tk_ws, p->tk_ws_bytes, f,
+                                     st);
     } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
@@ -941,6 +958,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   FS_REQUIRE(mode == 0 || !p->robust, "a FedNova aggregate and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(mode == 0 || !p->krum, "a FedNova aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(mode == 0 || !p->rfa, "a FedNova aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(mode == 0 || !p->topk, "a FedNova aggregate and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -975,6 +993,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(!p->robust, "SCAFFOLD and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "SCAFFOLD and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "SCAFFOLD and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "SCAFFOLD and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -1009,6 +1028,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   FS_REQUIRE(!p->robust, "a server optimizer and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "a server optimizer and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "a server optimizer and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "a server optimizer and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -1052,6 +1072,7 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   FS_REQUIRE(!p->robust, "q-FedAvg and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "q-FedAvg and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "q-FedAvg and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "q-FedAvg and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->qffl = 1;
   p->qf_g = d_g;
   p->qf_L = Lc;
@@ -1087,6 +1108,7 @@ extern "C" int fs_plan_set_robust(fs_plan* p, int on, int mode, double trim) {
   FS_REQUIRE(!p->qffl, "a robust aggregate and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->krum, "a robust aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "a robust aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "a robust aggregate and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->robust = mode;
   p->rb_trim = mode == FS_ROBUST_MEDIAN ? 0.0 : trim;
   return FS_OK;
@@ -1123,6 +1145,7 @@ extern "C" int fs_plan_set_krum(fs_plan* p, int on, double f_frac, int m_mode, i
   FS_REQUIRE(!p->qffl, "Krum and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "Krum and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->rfa, "Krum and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "Krum and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->krum = 1;
   p->kr_f = f_frac;
   p->kr_m = m_mode;
@@ -1165,6 +1188,7 @@ extern "C" int fs_plan_set_rfa(fs_plan* p, int on, int T, double nu, int init, i
   FS_REQUIRE(!p->qffl, "RFA and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
   FS_REQUIRE(!p->robust, "RFA and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "RFA and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->topk, "RFA and FedTopK exclude each other (fs_plan_set_topk(0) first)");
   p->rfa = 1;
   p->rf_T = T;
   p->rf_nu = nu;
@@ -1175,6 +1199,45 @@ extern "C" int fs_plan_set_rfa(fs_plan* p, int on, int T, double nu, int init, i
   p->rf_obj = d_obj;
   p->rf_ws = d_ws;
   p->rf_ws_bytes = ws_bytes;
+  return FS_OK;
+}
+
+// Additive to ABI 23: FedTopK on the AGGREGATE phases enqueued from now on (host state, read when a
+// round call enqueues).  on = 1: AGGREGATE launches fs_aggregate_topk over the round's rows with the
+// round's weights as q, d_W_g and the residuals d_e (nullptr: no memory) in place; TRAIN is
+// unchanged.  on = 0: the plain aggregate again.
+extern "C" int fs_plan_set_topk(fs_plan* p, int on, int64_t kcount, float* d_e, float* d_tau, int32_t* d_kept,
+                                void* d_sws, int64_t sws_bytes) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->topk = 0;
+    p->tk_count = 0;
+    p->tk_e = p->tk_tau = nullptr;
+    p->tk_kept = nullptr;
+    p->tk_ws = nullptr;
+    p->tk_ws_bytes = 0;
+    return FS_OK;
+  }
+  FS_REQUIRE(kcount >= 1 && kcount <= (int64_t)p->d.C * p->d.ld, "kcount must be in [1, C * ld]");
+  FS_REQUIRE(d_tau && d_kept, "null pointer");
+  FS_REQUIRE(!d_e || (d_e != p->d.d_W_g && d_e != p->d.d_W_out), "d_e must not be d_W_g or d_W_out");
+  FS_REQUIRE(!p->d.chained, "FedTopK needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  FS_REQUIRE(sws_bytes >= fs::aggregate_topk_ws_bytes(p->d.N, (int64_t)p->d.C * p->d.ld),
+             "d_sws is too small (fs_aggregate_topk_ws_bytes(N, C * ld))");
+  FS_REQUIRE(p->nova_mode == 0, "FedTopK and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "FedTopK and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "FedTopK and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "FedTopK and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "FedTopK and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "FedTopK and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "FedTopK and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  p->topk = 1;
+  p->tk_count = kcount;
+  p->tk_e = d_e;
+  p->tk_tau = d_tau;
+  p->tk_kept = d_kept;
+  p->tk_ws = d_sws;
+  p->tk_ws_bytes = sws_bytes;
   return FS_OK;
 }
 

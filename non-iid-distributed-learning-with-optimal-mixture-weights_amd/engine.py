@@ -564,6 +564,28 @@ class RoundPlan:
                    'fs_plan_set_rfa')
         self._rfa = (dist, b, obj, ws)
 
+    def set_topk(self, on, kcount=1, e=None, tau=None, kept=None, ws=None):
+        """fs_plan_set_topk: FedTopK on the AGGREGATE phases enqueued from now on -- fs_aggregate_topk over
+        the round's rows of ``W_out`` with the round's weights, ``W_g`` in place: every row's corrected
+        update thresholded at its ``kcount``-th largest magnitude (ties kept), the kept part folded onto
+        ``W_g``, the rest left in the client's row of ``e`` float32 [N, C * ld] (None: no memory, the
+        rest is dropped).  ``tau`` float32 [N] and ``kept`` int32 [N] take every round's thresholds (the
+        key's bits) and kept counts (by position); ``ws``: ``Aggregator.topk_ws()`` (uint8) or None.
+        TRAIN and EVAL are unchanged.  ``on`` false restores the plain aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_topk(self._h, 0, 0, None, None, None, None, 0), 'fs_plan_set_topk')
+            self._topk = None
+            return
+        if not (tau is not None and tau.is_cuda and tau.dtype == torch.float32 and tau.is_contiguous()
+                and kept is not None and kept.is_cuda and kept.dtype == torch.int32 and kept.is_contiguous()
+                and (e is None or (e.is_cuda and e.dtype == torch.float32 and e.is_contiguous()))
+                and (ws is None or (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()))):
+            raise ValueError('set_topk: tau (float32), kept (int32), e (float32 or None) and ws (uint8 or None) must '
+                             'be contiguous device tensors')
+        _lib.check(_lib.lib().fs_plan_set_topk(self._h, 1, int(kcount), _lib.ptr(e), _lib.ptr(tau), _lib.ptr(kept),
+                                               _lib.ptr(ws), 0 if ws is None else ws.numel()), 'fs_plan_set_topk')
+        self._topk = (e, tau, kept, ws)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -854,6 +876,66 @@ class Aggregator:
                    'fs_aggregate_rfa')
         return out
 
+    def topk_ws(self, M=None):
+        """A uint8 workspace for ``run_topk`` / ``topk_threshold`` at up to ``M`` rows (None: N):
+        fs_aggregate_topk_ws_bytes (the select keeps its counts in LDS: 0 bytes, a 16-byte tensor)."""
+        return torch.empty(max(16, topk_ws_bytes(self.N if M is None else int(M), self.len)), dtype=torch.uint8,
+                           device=self.ws.device)
+
+    def _topk_args(self, what, W_all, W_g, e, kcount, tau, kept, ws, sel, M, check):
+        def ok(x, dt, cnt):
+            return x is not None and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= cnt
+        rows = W_all.numel() // self.len
+        if not (M >= 1 and ok(W_all, torch.float32, self.len) and ok(W_g, torch.float32, self.len)
+                and ok(tau, torch.float32, M) and ok(kept, torch.int32, M)
+                and (e is None or ok(e, torch.float32, rows * self.len))
+                and (ws is None or ok(ws, torch.uint8, topk_ws_bytes(M, self.len)))):
+            raise ValueError('%s: W_all, W_g (float32), tau (float32 [M]), kept (int32 [M]), e (float32, as large as '
+                             'W_all, or None) and ws (uint8 or None) must be contiguous device tensors' % what)
+        if isinstance(kcount, bool) or not isinstance(kcount, (int, np.integer)) or not 1 <= kcount <= self.len:
+            raise ValueError('%s: kcount must be an int in [1, %d]' % (what, self.len))
+        if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous()
+                                    and sel.numel() == M):
+            raise ValueError('%s: sel must be a contiguous int32 device tensor of M ids' % what)
+        if sel is None and M > rows:
+            raise ValueError('%s: W_all has fewer than M rows' % what)
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('%s: sel must index rows of W_all, [0, %d)' % (what, rows))
+
+    def topk_threshold(self, W_all, W_g, e, kcount, tau, kept, sel=None, M=None, ws=None, check=True):
+        """fs_topk_threshold: stage A of ``run_topk`` over the rows ``sel`` of ``W_all`` (None: rows
+        0..M-1, M = N unless given) -- every row's corrected update a_k = (W_k - W_g) + e_k, its
+        ``kcount``-th largest magnitude key into ``tau`` (float32 [M], the key's bits) and the count of
+        keys at or above it into ``kept`` (int32 [M]).  With ``e`` (float32, rows as ``W_all``) it leaves
+        a_k IN e_k; ``e`` None: no memory, a_k = W_k - W_g.  ``check`` as in ``run_sel``."""
+        M = (self.N if M is None else int(M)) if sel is None else int(sel.numel())
+        self._topk_args('topk_threshold', W_all, W_g, e, kcount, tau, kept, ws, sel, M, check)
+        _lib.check(_lib.lib().fs_topk_threshold(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                                self.len, _lib.ptr(W_g), _lib.ptr(e), int(kcount), _lib.ptr(tau),
+                                                _lib.ptr(kept), _lib.ptr(ws), 0 if ws is None else ws.numel(),
+                                                _lib.stream_ptr()), 'fs_topk_threshold')
+        return tau, kept
+
+    def run_topk(self, W_all, q, kcount, W_g, e, tau, kept, sel=None, ws=None, check=True):
+        """fs_aggregate_topk: top-k sparsified uploads with error feedback over the rows ``sel`` of ``W_all``
+        (None: rows 0..len(q)-1), in place with x = ``W_g`` on entry: a_k = (W_k - x) + e_k, kept where its
+        magnitude key is at or above the row's ``kcount``-th largest (ties kept), ``W_g = x + sum_k
+        q_k * kept(a_k)`` folded as ``run_opt`` folds its delta, and e_k = the part not kept (``e`` float32 with
+        rows as ``W_all``, by client id; None: no memory).  ``tau`` float32 [M] (the threshold keys' bits) and
+        ``kept`` int32 [M] are written.  The rule: include/fedsim.h.  ``check`` as in ``run_sel``."""
+        M = int(q.numel())
+        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()):
+            raise ValueError('run_topk: q must be a contiguous float32 device tensor')
+        self._topk_args('run_topk', W_all, W_g, e, kcount, tau, kept, ws, sel, M, check)
+        _lib.check(_lib.lib().fs_aggregate_topk(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                                _lib.ptr(q), M, self.len, int(kcount), _lib.ptr(W_g), _lib.ptr(e),
+                                                _lib.ptr(tau), _lib.ptr(kept), _lib.ptr(self.ws), self.ws.numel(),
+                                                int(self.chunks), _lib.ptr(ws), 0 if ws is None else ws.numel(),
+                                                _lib.stream_ptr()), 'fs_aggregate_topk')
+        return W_g
+
     def run_robust(self, W_all, b, out, sel=None, check=True):
         """fs_aggregate_robust: the coordinate-wise trimmed mean of the rows ``sel`` of ``W_all`` (None:
         rows 0..N-1) with the trim count ``b``, 0 <= 2b < M: per coordinate the b smallest and the b
@@ -880,6 +962,12 @@ class Aggregator:
                                                   self.len, int(b), _lib.ptr(out), _lib.stream_ptr()),
                    'fs_aggregate_robust')
         return out
+
+
+def topk_ws_bytes(M, length):
+    """fs_aggregate_topk_ws_bytes: the bytes of workspace fs_aggregate_topk's select needs at M rows of
+    ``length`` floats (0: it keeps its counts in LDS)."""
+    return int(_lib.lib().fs_aggregate_topk_ws_bytes(int(M), int(length)))
 
 
 RFA_INITS = {'start': 0, 'mean': 1}      # FS_RFA_INIT_*

@@ -516,6 +516,33 @@ def _check_rfa_rounds(Ms, max_m):
                              % (t, M, max_m))
 
 
+def _check_topk(ratio, error_feedback, clients='parallel'):
+    """FedTopK's keyword checks (host only: before any device is touched)."""
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)):
+        raise ValueError('ratio must be a fraction in (0, 1] or an int count >= 1')
+    if isinstance(ratio, (int, np.integer)):
+        if ratio < 1:
+            raise ValueError('ratio as an int count must be >= 1')
+    elif not (0.0 < float(ratio) <= 1.0):
+        raise ValueError('ratio must be in (0, 1]')
+    if not isinstance(error_feedback, (bool, np.bool_)):
+        raise ValueError('error_feedback must be True or False')
+    if clients != 'parallel':
+        raise ValueError("FedTopK needs clients='parallel': a chained client's W_j - W_g holds its predecessors' work")
+
+
+def topk_count(ratio, C, D):
+    """The number of values a client uploads per round: ``ratio`` itself when it is an int count (at most
+    C * D), else max(1, floor(ratio * C * D)) for a fraction in (0, 1]."""
+    _check_topk(ratio, True)
+    n = int(C) * int(D)
+    if isinstance(ratio, (int, np.integer)):
+        if ratio > n:
+            raise ValueError('ratio as an int count must be at most C * D = %d' % n)
+        return int(ratio)
+    return max(1, int(math.floor(float(ratio) * n)))
+
+
 def byzantine_plan(N, byzantine):
     """``byzantine=`` checked and resolved (host only): None, or (sorted int64 ids, attack, scale, seed).
     ``ids``: the client ids given; ``fraction``: floor(fraction * N) ids fixed once from ``seed``
@@ -560,9 +587,17 @@ class Federation:
     def __init__(self, algo, X_train, y_train, X_test, y_test, validloader, type, num_classes, D, lr, epoch,
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
-                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None, rfa=None):
+                 server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None, rfa=None,
+                 topk=None):
         self.robust = algo == 'fedrobust'
         self.byz = None
+        self.topk = algo == 'fedtopk'
+        if self.topk:
+            # topk: dict(ratio=, error_feedback=) (tools.FedTopK)
+            tk = dict(topk or {})
+            self.tk_ratio, self.tk_memory = tk.get('ratio', 0.01), tk.get('error_feedback', True)
+            _check_topk(self.tk_ratio, self.tk_memory, clients)
+            self.tk_count = topk_count(self.tk_ratio, num_classes, D)
         self.rfa = algo == 'fedrfa'
         if self.rfa:
             # rfa: dict(iters=, nu=, init=, byzantine=) (tools.FedRFA); weighting is the keyword above
@@ -633,7 +668,7 @@ class Federation:
         self.sched = None
         if participation is not None:
             if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust', 'fedkrum',
-                            'fedrfa'):
+                            'fedrfa', 'fedtopk'):
                 raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
                                           'FedOpt, QFedAvg and FedRobust only')
             if self.chained:
@@ -671,6 +706,9 @@ class Federation:
                 raise NotImplementedError('FedRFA over more than one torch.distributed rank is not implemented')
             self.rf_M = [len(y_train)] * int(round) if self.sched is None else [len(S) for S in self.sched]
             _check_rfa_rounds(self.rf_M, engine.rfa_max_m())
+        if self.topk and nranks > 1:
+            # (a client's residual lives with its row; the thresholded fold has no all-reduce form here)
+            raise NotImplementedError('FedTopK over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -892,6 +930,15 @@ class Federation:
             self.rf_dist = torch.full((R, self.N), float('nan'), dtype=torch.float64, device=dev)
             self.rf_obj = torch.full((R, int(self.rf_T) + 2), float('nan'), dtype=torch.float64, device=dev)
             self.rf_ws = self.agg.rfa_ws()
+        if self.topk:
+            # FedAvg's round with fs_aggregate_topk as its aggregate; the residuals (all zero before round 0)
+            # stay with their clients, every round's thresholds and kept counts land in that round's row
+            # of the histories (the setter is called again before each round)
+            self.tk_e = torch.zeros(N, C, ld, device=dev, dtype=torch.float32) if self.tk_memory else None
+            self.tk_tau = torch.full((R, self.N), float('nan'), dtype=torch.float32, device=dev)
+            self.tk_kept = torch.full((R, self.N), -1, dtype=torch.int32, device=dev)
+            self.tk_ws = self.agg.topk_ws()
+            self.tk_rnorm = torch.zeros(R, dtype=torch.float64, device=dev) if stats is not None else None
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -976,6 +1023,8 @@ class Federation:
         if self.rfa:
             self.plan.set_rfa(True, self.rf_T, self.rf_nu, self.rf_init, self.rf_uniform, self.rf_dist[t],
                               self.rf_b[t], self.rf_obj[t], self.rf_ws)
+        if self.topk:
+            self.plan.set_topk(True, self.tk_count, self.tk_e, self.tk_tau[t], self.tk_kept[t], self.tk_ws)
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -1064,6 +1113,8 @@ class Federation:
         if self.fedopt and self.m_hist is not None:
             self.m_hist[t].copy_(self.opt_m)
             self.v_hist[t].copy_(self.opt_v)
+        if self.topk and self.tk_rnorm is not None and self.tk_e is not None:
+            self.tk_rnorm[t] = torch.linalg.vector_norm(self.tk_e, dtype=torch.float64)
         self.t += 1
         if self.chunk > 1:
             if t % self.chunk == 0 and t >= self.chunk:      # chunk c started: prepare chunk c + 1
@@ -1177,6 +1228,21 @@ class Federation:
                 self.stats['rfa_objective'] = self.rf_obj[:R].cpu().numpy()
                 if self.byz is not None:
                     self.stats['byzantine_ids'] = self.byz[0].copy()
+            if self.topk:
+                # (a row whose threshold is 0 keeps its padding columns too: they are no parameters)
+                th, kh = self.tk_tau[:R].cpu().numpy().astype(np.float64), self.tk_kept[:R].cpu().numpy()
+                kept, tau = np.full((R, self.N), np.nan), np.full((R, self.N), np.nan)
+                up, dense = np.zeros(R, np.int64), np.zeros(R, np.int64)
+                for t in range(R):
+                    S = np.arange(self.N) if self.sched is None else self.sched[t]
+                    kept[t, S] = np.minimum(kh[t, :len(S)], self.C * D)
+                    tau[t, S] = th[t, :len(S)]
+                    up[t], dense[t] = int(np.sum(kept[t, S])), len(S) * self.C * D
+                self.stats['topk_kept'], self.stats['topk_tau'] = kept, tau
+                self.stats['uplink_values'], self.stats['uplink_dense'] = up, dense
+                self.stats['residual_norm'] = self.tk_rnorm[:R].cpu().numpy()
+                if self.tk_e is not None:
+                    self.stats['residual'] = self.tk_e[:, :, :D].detach().clone()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -1467,6 +1533,36 @@ def FedRFA(X_train, y_train, X_test, y_test, type='classification', num_classes=
                 prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
                 options=options, participation=participation, sample_seed=sample_seed, weighting=weighting,
                 rfa=dict(iters=iters, nu=nu, init=init, byzantine=byzantine))
+
+
+def FedTopK(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+            batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, ratio=0.01,
+            error_feedback=True, stats=None, verbose=True, options=None, participation=None, sample_seed=0):
+    """Top-k sparsified uploads with error feedback (Aji & Heafield 2017; Stich, Cordonnier & Jaggi, NeurIPS
+    2018; Sattler et al. 2019; not in the reference): FedAvg's positional list, clients always parallel.
+    Local training is FedAvg's launch unchanged -- both tasks, ``prox=True``, any ``batch_size`` the task's
+    trainer accepts, ``participation`` -- and the server step is fs_aggregate_topk: every sampled client's
+    corrected update a_k = (W_k - W_g) + e_k is cut to the entries whose magnitude is at or above its
+    k-th largest, k = ``topk_count(ratio, C, D)`` (ties at the threshold are all kept, so a client may send
+    more than k values), the kept parts are folded onto ``W_g`` with FedAvg's weights p_k / sum_S p, and what
+    was not sent stays in the client's residual e_k for its next round.  ``error_feedback=False``: no
+    residual, the rest is dropped -- the variant known to stall under non-IID data.  The residual of a
+    client that sits a round out is carried unchanged.  Selection is by magnitude bits, so a NaN or an
+    Inf in an update is always transmitted: the rule carries no robustness claim.  ``ratio=1.0`` is
+    ``FedAvgM(server_lr=1.0, beta1=0.0)`` bit for bit.  The global generator is consumed exactly as by
+    ``FedAvg(clients='parallel')`` with the same ``participation``, and ``train_loss`` is FedAvg's.
+    ``stats['topk_kept']`` [R, N] float64 (the values each client sent; NaN where it was not sampled),
+    ``stats['topk_tau']`` [R, N] (its threshold magnitude), ``stats['uplink_values']`` [R] int64 (their
+    sum), ``stats['uplink_dense']`` [R] (M * C * D), ``stats['residual_norm']`` [R] (the norm of all
+    residuals after the round; 0 without memory) and ``stats['residual']`` [N, C, D] (with memory).
+    ValueError for a bad ``ratio`` or ``error_feedback``; NotImplementedError over more than one
+    torch.distributed rank."""
+    _check_topk(ratio, error_feedback)
+    topk_count(ratio, num_classes, D)
+    return _run('fedtopk', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed,
+                topk=dict(ratio=ratio, error_feedback=error_feedback))
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
