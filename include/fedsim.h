@@ -714,6 +714,72 @@ int fs_aggregate_topk(const float* d_W_all, int64_t stride, const int32_t* d_sel
                       float* d_ws, int64_t ws_floats, int chunks, void* d_sws, int64_t sws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * DP-FedAvg: per-client norm clipping and Gaussian noise on the aggregate (McMahan, Ramage, Talwar
+ * & Zhang, ICLR 2018; Geyer, Klein & Nabi 2017; adaptive clip: Andrew, Thakkar, McMahan & Ramaswamy,
+ * NeurIPS 2021).  Additive to ABI 23: the entry points below, FS_ABI_VERSION unchanged.
+ *
+ * The rule, over the round's M rows W_k (k the position in d_sel, NULL: rows 0..M-1) of d_W_all,
+ * each of len floats, x = d_W_g [len] on entry, the weights q_k (d_q [M]; NULL: every q_k =
+ * (float)(1.0 / M)), the clip S > 0 (+Inf: none), the noise multiplier z >= 0, the seed and the
+ * round t >= 0; all arithmetic is IEEE, every operation rounded separately, nothing contracted.
+ *   Norms.  d_k = fl(W_k - x);  n_k = sum_i d_k[i]^2, float squares summed in a fixed,
+ *     timing-independent order (float inside a wavefront's share of a row, at most 10 float
+ *     roundings on a square's path, double above it): within 10 x 2^-24 relative of the exact sum.
+ *   Coefficients (double).  r_k = sqrt(n_k);  s_k = 1 if r_k <= S, else S / r_k;
+ *     c_k = (float)(q_k * s_k), rounded once.  A row whose n_k is NaN or +Inf -- it holds a NaN, an
+ *     Inf, or squares that overflow float -- is DROPPED: c_k = 0, and it counts in `dropped`.
+ *   Fold.  Delta = sum_k (c_k == 0 ? +0 : fl(c_k * d_k)), a select (0 * NaN would poison the sum),
+ *     k ascending, folded exactly as fs_aggregate_opt folds its delta: the first term of a range the
+ *     term itself; regimes, sub-ranges, chunks and the stage-2 tree fs_aggregate's, chosen by M and
+ *     `chunks`, d_ws / ws_floats one partial per chunk.
+ *   Noise.  sigma = (z * S) * max_k q_k in double (max over all M rows; uniform q: z S / M, the
+ *     fixed-denominator estimator); z == 0: sigma = 0 and no noise term is formed.  Else
+ *     d_W_g[i] <- fl(fl(x[i] + Delta[i]) + fl((float)sigma * g[i])); z == 0: fl(x[i] + Delta[i]).
+ *   The field g depends on (seed, t, stream, i) alone, not on the launch geometry: the float4
+ *     position j = i / 4 takes the outputs w0..w3 of Philox4x32-10 at counter (j, t, stream, 0) and key
+ *     (seed mod 2^32, seed >> 32); u_m = (w_m + 0.5) * 2^-32; (g[4j], g[4j+1]) = sqrt(-2 ln u_0) *
+ *     (cos, sin)(2 pi u_1) and (g[4j+2], g[4j+3]) likewise from u_2, u_3, evaluated in double, each
+ *     rounded once to float; |g| <= sqrt(66 ln 2) < 6.77.  The model noise is stream 0.  cols_ld != 0:
+ *     the len floats are rows of cols_ld floats (a multiple of 4 that divides len) of which the first
+ *     cols_d are parameters; the others (a model's zero padding) take no noise term.  This is a
+ *     simulator's noise (floating-point Gaussian samples, a truncated tail), not a deployed
+ *     mechanism's, and no privacy accountant is provided.
+ *   Adaptive clip (adaptive != 0): the clip of the round is read from d_clip[0] on the device (S is
+ *     then only checked) and, after every c_k has been formed from it, d_clip[0] <- S_next =
+ *     S * exp(-eta * ((b + sigma_b * g_b) / M - gamma)) in double, b = #{k not dropped : r_k <= S} and
+ *     g_b the first normal of the block at counter (0, t, 1, 0) (stream 1).  Else S_next = S.
+ *   State.  d_state [FS_DP_STATE] doubles: {S used, sigma, b, dropped, S_next}; d_r[k] = r_k (NaN or
+ *     +Inf for a dropped row); d_c[k] = c_k.
+ * fs_dp_norms: the norm pass alone, n_k into d_n [M] doubles; reads the M rows once, coalesced.
+ * fs_dp_coef: the coefficient kernel alone from d_n (one workgroup): d_c, d_r, d_state, d_clip.
+ * fs_dp_noise: writes g [len] for (seed, t, stream).
+ * fs_aggregate_dp: the three stages (4 to 5 launches): reads the rows twice, writes len floats of
+ * d_W_g in place.  d_sws of sws_bytes >= fs_aggregate_dp_ws_bytes(M, len) bytes holds the norms and
+ * their partial table.  No atomics, no cross-workgroup wait, no allocation, no host
+ * synchronisation; the same bits on every call and for the same rows gathered from a larger buffer.
+ * With S = +Inf, z = 0 and every q_k > 0, d_W_g is bitwise what fs_aggregate_opt(FS_OPT_AVGM,
+ * beta1 = 0, eta = 1) leaves with the same q, chunks and workspace.  tests/dp_restatement.py restates
+ * the rule in numpy.
+ * FS_EINVAL, and nothing is written then, for M < 1, S <= 0 or NaN, z < 0 or not finite, z > 0 with
+ * S = +Inf, t < 0, len or stride no multiple of 4, stride < len, a null pointer (d_sel and d_q may be
+ * NULL; d_clip unless adaptive), a workspace that is too small, or adaptive with S = +Inf, gamma
+ * outside [0, 1], or eta or sigma_b negative or not finite.
+ * ------------------------------------------------------------------------- */
+#define FS_DP_STATE 5
+int64_t fs_aggregate_dp_ws_bytes(int M, int64_t len);
+int fs_dp_norms(const float* d_W_all, int64_t stride, const int32_t* d_sel, int M, int64_t len, const float* d_W_g,
+                double* d_n, void* d_sws, int64_t sws_bytes, void* stream);
+int fs_dp_coef(const double* d_n, const float* d_q, int M, double S, double z, uint64_t seed, int t, int adaptive,
+               double gamma, double eta, double sigma_b, double* d_clip, float* d_c, double* d_r, double* d_state,
+               void* stream);
+int fs_dp_noise(uint64_t seed, int t, int noise_stream, int64_t len, float* d_g, void* stream);
+int fs_aggregate_dp(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M, int64_t len,
+                    double S, double z, uint64_t seed, int t, int adaptive, double gamma, double eta, double sigma_b,
+                    double* d_clip, int64_t cols_ld, int64_t cols_d, float* d_W_g, float* d_c, double* d_r,
+                    double* d_state, float* d_ws, int64_t ws_floats, int chunks, void* d_sws, int64_t sws_bytes,
+                    void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Test evaluation. Replaces test_loop + comp_accuracy + Meter (tools.py:218-237,
  * 82-96, 99-148): d_out[0] = mean cross-entropy over n rows, d_out[1] = top-1
  * accuracy in percent.  Ties in the arg-max go to the lowest class index.
@@ -1223,6 +1289,24 @@ int fs_plan_set_rfa(fs_plan* plan, int on, int T, double nu, int init, int unifo
  * fs_plan_set_robust, fs_plan_set_krum and fs_plan_set_rfa refuse in turn while it is on. */
 int fs_plan_set_topk(fs_plan* plan, int on, int64_t kcount, float* d_e, float* d_tau, int32_t* d_kept, void* d_sws,
                      int64_t sws_bytes);
+
+/* (additive to ABI 23) DP-FedAvg on this plan's AGGREGATE phase.  Host state read when the next round
+ * call enqueues, as fs_plan_set_topk's.  on = 1: AGGREGATE launches fs_aggregate_dp over the round's
+ * rows of d_W_out (all N, or the subset call's M ids) with the round's normalised weights as q
+ * (uniform != 0: 1 / M), the round call's t as the noise round, d_W_g in place, the plan's
+ * aggregation workspace and chunks, and the pending finaliser of a deferred evaluation on the fold.
+ * d_c [N] float, d_r [N] double and d_state [FS_DP_STATE] double take the round's coefficients, norms
+ * (by position) and state; d_clip [1] double is the adaptive clip (adaptive != 0: set to S before
+ * the first round by the caller, updated on the device every round; else ignored); cols = D, the
+ * model's real columns of its ld (the padding takes no noise: it stays exactly 0); d_sws of
+ * sws_bytes >= fs_aggregate_dp_ws_bytes(N, C * ld) bytes.  TRAIN and EVAL are unchanged.  on = 0
+ * restores the plain aggregate.  FS_EINVAL for a chained plan, the rule's refusals of
+ * fs_aggregate_dp, a null d_c, d_r, d_state or d_sws, a workspace that is too small, a nova mode
+ * other than 0, SCAFFOLD on, a server-optimizer rule set, q-FedAvg on, a robust aggregate on, Krum
+ * on, RFA on or FedTopK on; their setters refuse in turn while it is on. */
+int fs_plan_set_dp(fs_plan* plan, int on, double S, double z, uint64_t seed, int uniform, int adaptive, double gamma,
+                   double eta, double sigma_b, double* d_clip, int64_t cols, float* d_c, double* d_r, double* d_state,
+                   void* d_sws, int64_t sws_bytes);
 
 /* ABI 7, measurement: timing events recorded without a system-scope release (so timing a
  * launch inside a round does not stall the next one); elapsed_ms synchronises on `end`. */

@@ -106,6 +106,21 @@ _SIGS = {
                                     C.c_void_p, C.c_int64, C.c_void_p]),
     'fs_plan_set_topk': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64]),
+    # DP-FedAvg, clipped updates and Gaussian noise (additive to ABI 23)
+    'fs_aggregate_dp_ws_bytes': (C.c_int64, [C.c_int, C.c_int64]),
+    'fs_dp_norms': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_dp_coef': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_int, C.c_int,
+                             C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
+    'fs_dp_noise': (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    'fs_aggregate_dp': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double,
+                                  C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                  C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    'fs_plan_set_dp': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_int, C.c_int,
+                                 C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64]),
     'fs_eval_ws_doubles': (C.c_int64, [C.c_int]),
     'fs_eval': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p]),
@@ -407,6 +422,8 @@ KERNEL_SOURCES = {
     'aggregate_rfa': ('aggregate_rfa.hip', 'aggregate_sel.h', 'finalize.h', 'common.h'),
     'aggregate_topk': ('aggregate_topk.hip', 'aggregate_fold.h', 'aggregate_geom.h', 'aggregate_sel.h', 'finalize.h',
                        'common.h'),
+    'aggregate_dp': ('aggregate_dp.hip', 'aggregate_fold.h', 'aggregate_geom.h', 'aggregate_sel.h', 'finalize.h',
+                     'lanes.h', 'common.h'),
 }
 
 

@@ -63,4 +63,12 @@ int aggregate_topk_launch(const float* d_W_all, int64_t stride, const int32_t* d
                           const EvalFinalize* fin, hipStream_t st);
 int64_t aggregate_topk_ws_bytes(int M, int64_t len);
 
+// fs_aggregate_dp (aggregate_dp.hip) with an optional finaliser, which rides on the clipped fold
+int aggregate_dp_launch(const float* d_W_all, int64_t stride, const int32_t* d_sel, const float* d_q, int M,
+                        int64_t len, double S, double z, uint64_t seed, int t, int adaptive, double gamma, double eta,
+                        double sigma_b, double* d_clip, int64_t cols_ld, int64_t cols_d, float* d_W_g, float* d_c,
+                        double* d_r, double* d_state, float* d_ws, int64_t ws_floats, int chunks, void* d_sws,
+                        int64_t sws_bytes, const EvalFinalize* fin, hipStream_t st);
+int64_t aggregate_dp_ws_bytes(int M, int64_t len);
+
 }  // namespace fs

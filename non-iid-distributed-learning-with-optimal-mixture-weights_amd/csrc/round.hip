@@ -59,6 +59,11 @@
 // (aggregate_topk.hip), the per-row top-k threshold of the round's corrected updates and their
 // thresholded fold onto d_W_g, the clients' residuals updated in place.  TRAIN is untouched, and the
 // finaliser rides on the fold.
+//
+// DP-FedAvg (additive to ABI 23, fs_plan_set_dp): AGGREGATE launches fs_aggregate_dp
+// (aggregate_dp.hip), the norm pass over the round's updates, their clip coefficients and the clipped
+// fold onto d_W_g with the round's Gaussian noise, t the round index of the call.  TRAIN is
+// untouched, and the finaliser rides on the fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -246,6 +251,19 @@ struct fs_plan {
   int32_t* tk_kept = nullptr;         // [N]
   void* tk_ws = nullptr;
   int64_t tk_ws_bytes = 0;
+  // fs_plan_set_dp: AGGREGATE is fs_aggregate_dp
+  int dp = 0;
+  double dp_S = 0.0, dp_z = 0.0;
+  uint64_t dp_seed = 0;
+  int dp_uniform = 0, dp_adaptive = 0;
+  int64_t dp_cols = 0;                // the model's real columns D <= ld: the padding takes no noise
+  double dp_gamma = 0.0, dp_eta = 0.0, dp_sigma_b = 0.0;
+  double* dp_clip = nullptr;          // [1] the adaptive clip (nullptr: fixed)
+  float* dp_c = nullptr;              // [N]
+  double* dp_r = nullptr;             // [N]
+  double* dp_state = nullptr;         // [FS_DP_STATE]
+  void* dp_ws = nullptr;
+  int64_t dp_ws_bytes = 0;
   hipStream_t copy = nullptr;
   hipEvent_t uploaded[2] = {nullptr, nullptr};
   hipEvent_t consumed[2] = {nullptr, nullptr};
@@ -918,6 +936,11 @@ static int plan_round(fs_plan* p, int t, float lr, int phases, const float* d_p_
       rc = fs::aggregate_topk_launch(d.d_W_out, len, sel, pw, M, len, p->tk_count, d.d_W_g, p->tk_e, p->tk_tau,
                                      p->tk_kept, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, p->tk_ws, p->tk_ws_bytes, f,
                                      st);
+    } else if (p->dp) {
+      rc = fs::aggregate_dp_launch(d.d_W_out, len, sel, p->dp_uniform ? nullptr : pw, M, len, p->dp_S, p->dp_z,
+                                   p->dp_seed, t, p->dp_adaptive, p->dp_gamma, p->dp_eta, p->dp_sigma_b, p->dp_clip,
+                                   d.ld, p->dp_cols, d.d_W_g, p->dp_c, p->dp_r, p->dp_state, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks,
+                                   p->dp_ws, p->dp_ws_bytes, f, st);
     } else if (p->nova_mode)
       rc = fs::aggregate_nova_launch(d.d_W_out, len, sel, pw, p->nova_b, p->nova_te, p->nova_s0, p->nova_mode, d.d_W_g,
                                      M, len, d.d_W_g, d.d_agg_ws, d.agg_ws_floats, d.agg_chunks, f, st);
@@ -959,6 +982,7 @@ extern "C" int fs_plan_set_nova(fs_plan* p, int mode, const float* d_b, float te
   FS_REQUIRE(mode == 0 || !p->krum, "a FedNova aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(mode == 0 || !p->rfa, "a FedNova aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(mode == 0 || !p->topk, "a FedNova aggregate and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(mode == 0 || !p->dp, "a FedNova aggregate and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->nova_mode = mode;
   p->nova_b = mode == FS_NOVA_REFERENCE ? d_b : nullptr;
   p->nova_te = te;
@@ -994,6 +1018,7 @@ extern "C" int fs_plan_set_scaffold(fs_plan* p, int on, float* d_c, float* d_ci,
   FS_REQUIRE(!p->krum, "SCAFFOLD and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "SCAFFOLD and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(!p->topk, "SCAFFOLD and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "SCAFFOLD and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   FS_REQUIRE(p->scaffold || (p->eval_pending < 0 && p->fin_pending < 0),
              "the plan holds a pending evaluation (fs_plan_eval_flush first)");
   p->scaffold = 1;
@@ -1029,6 +1054,7 @@ extern "C" int fs_plan_set_server_opt(fs_plan* p, int rule, float* d_m, float* d
   FS_REQUIRE(!p->krum, "a server optimizer and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "a server optimizer and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(!p->topk, "a server optimizer and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "a server optimizer and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->opt_rule = rule;
   p->opt_m = d_m;
   p->opt_v = rule == FS_OPT_AVGM ? nullptr : d_v;
@@ -1073,6 +1099,7 @@ extern "C" int fs_plan_set_qffl(fs_plan* p, int on, const float* d_g, double Lc,
   FS_REQUIRE(!p->krum, "q-FedAvg and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "q-FedAvg and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(!p->topk, "q-FedAvg and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "q-FedAvg and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->qffl = 1;
   p->qf_g = d_g;
   p->qf_L = Lc;
@@ -1109,6 +1136,7 @@ extern "C" int fs_plan_set_robust(fs_plan* p, int on, int mode, double trim) {
   FS_REQUIRE(!p->krum, "a robust aggregate and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "a robust aggregate and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(!p->topk, "a robust aggregate and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "a robust aggregate and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->robust = mode;
   p->rb_trim = mode == FS_ROBUST_MEDIAN ? 0.0 : trim;
   return FS_OK;
@@ -1146,6 +1174,7 @@ extern "C" int fs_plan_set_krum(fs_plan* p, int on, double f_frac, int m_mode, i
   FS_REQUIRE(!p->robust, "Krum and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->rfa, "Krum and RFA exclude each other (fs_plan_set_rfa(0) first)");
   FS_REQUIRE(!p->topk, "Krum and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "Krum and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->krum = 1;
   p->kr_f = f_frac;
   p->kr_m = m_mode;
@@ -1189,6 +1218,7 @@ extern "C" int fs_plan_set_rfa(fs_plan* p, int on, int T, double nu, int init, i
   FS_REQUIRE(!p->robust, "RFA and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "RFA and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->topk, "RFA and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  FS_REQUIRE(!p->dp, "RFA and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->rfa = 1;
   p->rf_T = T;
   p->rf_nu = nu;
@@ -1231,6 +1261,7 @@ extern "C" int fs_plan_set_topk(fs_plan* p, int on, int64_t kcount, float* d_e, 
   FS_REQUIRE(!p->robust, "FedTopK and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
   FS_REQUIRE(!p->krum, "FedTopK and Krum exclude each other (fs_plan_set_krum(0) first)");
   FS_REQUIRE(!p->rfa, "FedTopK and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->dp, "FedTopK and DP-FedAvg exclude each other (fs_plan_set_dp(0) first)");
   p->topk = 1;
   p->tk_count = kcount;
   p->tk_e = d_e;
@@ -1238,6 +1269,61 @@ extern "C" int fs_plan_set_topk(fs_plan* p, int on, int64_t kcount, float* d_e, 
   p->tk_kept = d_kept;
   p->tk_ws = d_sws;
   p->tk_ws_bytes = sws_bytes;
+  return FS_OK;
+}
+
+// Additive to ABI 23: DP-FedAvg on the AGGREGATE phases enqueued from now on (host state, read when a
+// round call enqueues).  on = 1: AGGREGATE launches fs_aggregate_dp over the round's rows with the
+// round's weights as q (uniform: 1 / M), the call's t as the noise round, d_W_g in place; TRAIN is
+// unchanged.  on = 0: the plain aggregate again.
+extern "C" int fs_plan_set_dp(fs_plan* p, int on, double S, double z, uint64_t seed, int uniform, int adaptive,
+                              double gamma, double eta, double sigma_b, double* d_clip, int64_t cols, float* d_c,
+                              double* d_r, double* d_state, void* d_sws, int64_t sws_bytes) {
+  FS_REQUIRE(p, "bad arguments");
+  if (!on) {
+    p->dp = 0;
+    p->dp_clip = p->dp_r = p->dp_state = nullptr;
+    p->dp_c = nullptr;
+    p->dp_ws = nullptr;
+    p->dp_ws_bytes = 0;
+    return FS_OK;
+  }
+  const double dmax = 1.7976931348623157e308;
+  FS_REQUIRE(S > 0.0, "the clip S must be > 0 (+Inf: no clipping)");
+  FS_REQUIRE(z >= 0.0 && z <= dmax, "the noise multiplier z must be finite and >= 0");
+  FS_REQUIRE(z == 0.0 || S <= dmax, "noise (z > 0) needs a finite clip");
+  FS_REQUIRE(!adaptive || (d_clip && S <= dmax && gamma >= 0.0 && gamma <= 1.0 && eta >= 0.0 && eta <= dmax &&
+                           sigma_b >= 0.0 && sigma_b <= dmax),
+             "the adaptive clip needs d_clip, a finite clip, a quantile in [0, 1] and finite lr, count noise >= 0");
+  FS_REQUIRE(d_c && d_r && d_state && d_sws, "null pointer");
+  FS_REQUIRE(cols >= 1 && cols <= p->d.ld, "cols (the model's real columns) must be in [1, ld]");
+  FS_REQUIRE(!p->d.chained, "DP-FedAvg needs parallel clients (a chained client's W_j - W_g holds its predecessors' work)");
+  FS_REQUIRE(sws_bytes >= fs::aggregate_dp_ws_bytes(p->d.N, (int64_t)p->d.C * p->d.ld),
+             "d_sws is too small (fs_aggregate_dp_ws_bytes(N, C * ld))");
+  FS_REQUIRE(p->nova_mode == 0, "DP-FedAvg and a FedNova aggregate exclude each other (fs_plan_set_nova(0) first)");
+  FS_REQUIRE(!p->scaffold, "DP-FedAvg and SCAFFOLD exclude each other (fs_plan_set_scaffold(0) first)");
+  FS_REQUIRE(p->opt_rule == 0, "DP-FedAvg and a server optimizer exclude each other (fs_plan_set_server_opt(0) first)");
+  FS_REQUIRE(!p->qffl, "DP-FedAvg and q-FedAvg exclude each other (fs_plan_set_qffl(0) first)");
+  FS_REQUIRE(!p->robust, "DP-FedAvg and a robust aggregate exclude each other (fs_plan_set_robust(0) first)");
+  FS_REQUIRE(!p->krum, "DP-FedAvg and Krum exclude each other (fs_plan_set_krum(0) first)");
+  FS_REQUIRE(!p->rfa, "DP-FedAvg and RFA exclude each other (fs_plan_set_rfa(0) first)");
+  FS_REQUIRE(!p->topk, "DP-FedAvg and FedTopK exclude each other (fs_plan_set_topk(0) first)");
+  p->dp = 1;
+  p->dp_S = S;
+  p->dp_z = z;
+  p->dp_seed = seed;
+  p->dp_uniform = uniform ? 1 : 0;
+  p->dp_adaptive = adaptive ? 1 : 0;
+  p->dp_cols = cols;
+  p->dp_gamma = gamma;
+  p->dp_eta = eta;
+  p->dp_sigma_b = sigma_b;
+  p->dp_clip = adaptive ? d_clip : nullptr;
+  p->dp_c = d_c;
+  p->dp_r = d_r;
+  p->dp_state = d_state;
+  p->dp_ws = d_sws;
+  p->dp_ws_bytes = sws_bytes;
   return FS_OK;
 }
 

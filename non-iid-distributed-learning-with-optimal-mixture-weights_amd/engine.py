@@ -586,6 +586,40 @@ class RoundPlan:
                                                _lib.ptr(ws), 0 if ws is None else ws.numel()), 'fs_plan_set_topk')
         self._topk = (e, tau, kept, ws)
 
+    def set_dp(self, on, clip=1.0, noise_multiplier=0.0, seed=0, uniform=False, adaptive=None, clip_dev=None,
+               c=None, r=None, state=None, ws=None, cols=None):
+        """fs_plan_set_dp: DP-FedAvg on the AGGREGATE phases enqueued from now on -- fs_aggregate_dp over the
+        round's rows of ``W_out`` with the round's weights (``uniform``: 1 / M), ``W_g`` in place: every update
+        clipped to the norm ``clip``, the clipped updates folded onto ``W_g`` and Gaussian noise of standard
+        deviation ``noise_multiplier * clip * max_k q_k`` added from the Philox field of (``seed``, the round
+        call's t).  ``adaptive``: None or dict(quantile, lr, count_noise); the clip then lives in ``clip_dev``
+        (float64 [1], set to ``clip`` by the caller before the first round) and is updated on the device.
+        ``c`` float32 [N], ``r`` float64 [N] and ``state`` float64 [DP_STATE] take every round's coefficients,
+        update norms (by position) and state; ``ws``: ``Aggregator.dp_ws()`` (uint8); ``cols``: D, the model's
+        real columns (the padding up to ld takes no noise).  TRAIN and EVAL are unchanged.  ``on`` false restores the plain aggregate."""
+        if not on:
+            _lib.check(_lib.lib().fs_plan_set_dp(self._h, 0, 0.0, 0.0, 0, 0, 0, 0.0, 0.0, 0.0, None, 0, None, None,
+                                                 None, None, 0), 'fs_plan_set_dp')
+            self._dp = None
+            return
+
+        def ok(x, dt):
+            return x is not None and x.is_cuda and x.dtype == dt and x.is_contiguous()
+        if not (ok(c, torch.float32) and ok(r, torch.float64) and ok(state, torch.float64)
+                and state.numel() >= DP_STATE and ok(ws, torch.uint8)
+                and (adaptive is None or (ok(clip_dev, torch.float64) and clip_dev.numel() >= 1))):
+            raise ValueError('set_dp: c (float32), r, state (float64), ws (uint8) and, with adaptive, clip_dev '
+                             '(float64) must be contiguous device tensors')
+        ad = dict(adaptive or {})
+        _lib.check(_lib.lib().fs_plan_set_dp(self._h, 1, float(clip), float(noise_multiplier), int(seed),
+                                             int(bool(uniform)), int(adaptive is not None),
+                                             float(ad.get('quantile', 0.0)), float(ad.get('lr', 0.0)),
+                                             float(ad.get('count_noise', 0.0)),
+                                             _lib.ptr(clip_dev) if adaptive is not None else None, int(cols),
+                                             _lib.ptr(c), _lib.ptr(r), _lib.ptr(state), _lib.ptr(ws), ws.numel()),
+                   'fs_plan_set_dp')
+        self._dp = (clip_dev, c, r, state, ws)
+
     def eval_flush(self):
         """fs_plan_eval_flush (ABI 15): complete any evaluation still deferred, so the eval
         history is final on the current stream."""
@@ -936,6 +970,114 @@ class Aggregator:
                                                 _lib.stream_ptr()), 'fs_aggregate_topk')
         return W_g
 
+    def dp_ws(self, M=None):
+        """A uint8 workspace for ``run_dp`` / ``dp_norms`` at up to ``M`` rows (None: N): fs_aggregate_dp_ws_bytes
+        (the norms and their partial table)."""
+        return torch.empty(max(16, dp_ws_bytes(self.N if M is None else int(M), self.len)), dtype=torch.uint8,
+                           device=self.ws.device)
+
+    def _dp_rows(self, what, W_all, W_g, ws, sel, M, check):
+        def ok(x, dt, cnt):
+            return x is not None and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= cnt
+        rows = W_all.numel() // self.len
+        if not (M >= 1 and ok(W_all, torch.float32, self.len) and ok(W_g, torch.float32, self.len)
+                and ok(ws, torch.uint8, dp_ws_bytes(M, self.len))):
+            raise ValueError('%s: W_all, W_g (float32) and ws (uint8, dp_ws()) must be contiguous device tensors' % what)
+        if sel is not None and not (sel.is_cuda and sel.dtype == torch.int32 and sel.is_contiguous()
+                                    and sel.numel() == M):
+            raise ValueError('%s: sel must be a contiguous int32 device tensor of M ids' % what)
+        if sel is None and M > rows:
+            raise ValueError('%s: W_all has fewer than M rows' % what)
+        if check and sel is not None:
+            lo, hi = int(sel.min().item()), int(sel.max().item())
+            if lo < 0 or hi >= rows:
+                raise ValueError('%s: sel must index rows of W_all, [0, %d)' % (what, rows))
+
+    @staticmethod
+    def _dp_outs(what, M, c, r, state, q, clip_dev, adaptive):
+        def ok(x, dt, cnt):
+            return x is not None and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() >= cnt
+        if not (ok(c, torch.float32, M) and ok(r, torch.float64, M) and ok(state, torch.float64, DP_STATE)
+                and (q is None or (ok(q, torch.float32, M) and q.numel() == M))
+                and (adaptive is None or ok(clip_dev, torch.float64, 1))):
+            raise ValueError('%s: c (float32 [M]), r (float64 [M]), state (float64 [%d]), q (float32 [M] or None) and, '
+                             'with adaptive, clip_dev (float64 [1]) must be contiguous device tensors'
+                             % (what, DP_STATE))
+
+    @staticmethod
+    def _dp_rule(clip, noise_multiplier, seed, t, adaptive):
+        ad = dict(adaptive or {})
+        return (float(clip), float(noise_multiplier), int(seed), int(t), int(adaptive is not None),
+                float(ad.get('quantile', 0.0)), float(ad.get('lr', 0.0)), float(ad.get('count_noise', 0.0)))
+
+    def dp_norms(self, W_all, W_g, n, sel=None, M=None, ws=None, check=True):
+        """fs_dp_norms: the squared norms of the updates ``W_all[row_k] - W_g`` of the rows ``sel`` (None: rows
+        0..M-1, M = N unless given) into ``n`` float64 [M]: float squares summed in a fixed order, the same
+        bits on every call.  ``check`` as in ``run_sel``."""
+        M = (self.N if M is None else int(M)) if sel is None else int(sel.numel())
+        ws = self.dp_ws(M) if ws is None else ws
+        self._dp_rows('dp_norms', W_all, W_g, ws, sel, M, check)
+        if not (n is not None and n.is_cuda and n.dtype == torch.float64 and n.is_contiguous() and n.numel() >= M):
+            raise ValueError('dp_norms: n must be a contiguous float64 device tensor of M values')
+        _lib.check(_lib.lib().fs_dp_norms(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel), M,
+                                          self.len, _lib.ptr(W_g), _lib.ptr(n), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr()), 'fs_dp_norms')
+        return n
+
+    def dp_coef(self, n, q, clip, noise_multiplier, c, r, state, seed=0, t=0, adaptive=None, clip_dev=None):
+        """fs_dp_coef: from the squared norms ``n`` float64 [M] and the weights ``q`` float32 [M] (None: 1 / M)
+        the clip coefficients ``c`` float32 [M], the norms ``r`` float64 [M] and ``state`` float64 [DP_STATE] =
+        (clip, sigma, b, dropped, clip_next).  ``adaptive``: dict(quantile, lr, count_noise); the clip is then
+        read from and written back to ``clip_dev`` float64 [1]."""
+        M = int(n.numel())
+        if not (n.is_cuda and n.dtype == torch.float64 and n.is_contiguous()):
+            raise ValueError('dp_coef: n must be a contiguous float64 device tensor')
+        self._dp_outs('dp_coef', M, c, r, state, q, clip_dev, adaptive)
+        S, z, seed, t, ad, ga, eta, sb = self._dp_rule(clip, noise_multiplier, seed, t, adaptive)
+        _lib.check(_lib.lib().fs_dp_coef(_lib.ptr(n), _lib.ptr(q), M, S, z, seed, t, ad, ga, eta, sb,
+                                         _lib.ptr(clip_dev) if ad else None, _lib.ptr(c), _lib.ptr(r),
+                                         _lib.ptr(state), _lib.stream_ptr()), 'fs_dp_coef')
+        return c, r, state
+
+    def dp_noise(self, seed, t, g, stream=0):
+        """fs_dp_noise: the Gaussian field of (``seed``, ``t``, ``stream``) into ``g`` float32 (a multiple of 4
+        values): Philox4x32-10 at counter (i // 4, t, stream, 0), Box-Muller in double.  Stream 0 is the
+        model noise of ``run_dp``."""
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
+            raise ValueError('dp_noise: g must be a contiguous float32 device tensor')
+        _lib.check(_lib.lib().fs_dp_noise(int(seed), int(t), int(stream), g.numel(), _lib.ptr(g),
+                                          _lib.stream_ptr()), 'fs_dp_noise')
+        return g
+
+    def run_dp(self, W_all, q, clip, noise_multiplier, W_g, c, r, state, seed=0, t=0, adaptive=None, clip_dev=None,
+               sel=None, M=None, ws=None, check=True, cols=None):
+        """fs_aggregate_dp: DP-FedAvg's server step over the rows ``sel`` of ``W_all`` (None: rows 0..M-1, M =
+        len(q), or N with ``q`` None), in place with x = ``W_g`` on entry: every update W_k - x scaled to a norm
+        of at most ``clip`` (rows with a non-finite norm dropped), folded with ``q`` (None: 1 / M) as ``run_opt``
+        folds its delta, and ``noise_multiplier * clip * max q`` times the field of (``seed``, ``t``) added.
+        ``c``, ``r``, ``state``, ``adaptive`` and ``clip_dev`` as in ``dp_coef``.  ``cols``: None, or (ld, D) for
+        rows of ld floats of which the first D are parameters (the others take no noise).  The rule: include/fedsim.h.
+        ``check`` as in ``run_sel``."""
+        if sel is not None:
+            M = int(sel.numel())
+        elif q is not None:
+            M = int(q.numel())
+        else:
+            M = self.N if M is None else int(M)
+        ws = self.dp_ws(M) if ws is None else ws
+        self._dp_rows('run_dp', W_all, W_g, ws, sel, M, check)
+        self._dp_outs('run_dp', M, c, r, state, q, clip_dev, adaptive)
+        S, z, seed, t, ad, ga, eta, sb = self._dp_rule(clip, noise_multiplier, seed, t, adaptive)
+        _lib.check(_lib.lib().fs_aggregate_dp(_lib.ptr(W_all), self.len, None if sel is None else _lib.ptr(sel),
+                                              _lib.ptr(q), M, self.len, S, z, seed, t, ad, ga, eta, sb,
+                                              _lib.ptr(clip_dev) if ad else None,
+                                              0 if cols is None else int(cols[0]), 0 if cols is None else int(cols[1]),
+                                              _lib.ptr(W_g), _lib.ptr(c),
+                                              _lib.ptr(r), _lib.ptr(state), _lib.ptr(self.ws), self.ws.numel(),
+                                              int(self.chunks), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   'fs_aggregate_dp')
+        return W_g
+
     def run_robust(self, W_all, b, out, sel=None, check=True):
         """fs_aggregate_robust: the coordinate-wise trimmed mean of the rows ``sel`` of ``W_all`` (None:
         rows 0..N-1) with the trim count ``b``, 0 <= 2b < M: per coordinate the b smallest and the b
@@ -968,6 +1110,15 @@ def topk_ws_bytes(M, length):
     """fs_aggregate_topk_ws_bytes: the bytes of workspace fs_aggregate_topk's select needs at M rows of
     ``length`` floats (0: it keeps its counts in LDS)."""
     return int(_lib.lib().fs_aggregate_topk_ws_bytes(int(M), int(length)))
+
+
+DP_STATE = 5      # FS_DP_STATE: clip, sigma, b, dropped, clip_next
+
+
+def dp_ws_bytes(M, length):
+    """fs_aggregate_dp_ws_bytes: the bytes of workspace fs_aggregate_dp's norm pass needs at M rows of
+    ``length`` floats (the norms and their partial table)."""
+    return int(_lib.lib().fs_aggregate_dp_ws_bytes(int(M), int(length)))
 
 
 RFA_INITS = {'start': 0, 'mean': 1}      # FS_RFA_INIT_*

@@ -66,6 +66,8 @@ EXTRA_KRUM = ['Krum', 'MultiKrum']
 EXTRA_RFA = ['FedRFA']
 # FedTopK, top-k sparsified uploads with error feedback (not in the reference) after RFA's row; a list of its own too
 EXTRA_TOPK = ['FedTopK']
+# DPFedAvg, clipped updates and Gaussian noise (not in the reference) after FedTopK's row; a list of its own too
+EXTRA_DP = ['DPFedAvg']
 
 
 def prepare(dataset, D, num_partitions, alpha_Dirk, params, data_dir, synth=None, verbose=True):
@@ -106,17 +108,18 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
         sample_seed=0, server_lr=None, server_beta1=0.9, server_beta2=0.99, server_tau=1e-3, qffl_q=1.0,
         qffl_weighting='size', robust_trim=0.1, byzantine_fraction=0.0, byzantine_attack='sign_flip',
         byzantine_scale=1.0, krum_f=0.1, rfa_iters=3, rfa_nu=1e-6, rfa_init='start', rfa_weighting='size',
-        topk_ratio=0.01, topk_memory=True):
+        topk_ratio=0.01, topk_memory=True, dp_clip=1.0, dp_noise_multiplier=1.0, dp_noise_seed=0,
+        dp_weighting='uniform', dp_adaptive_quantile=None, dp_adaptive_lr=0.2):
     if client_eval not in (None, 'test', 'val', 'both'):
         raise ValueError("client_eval must be None, 'test', 'val' or 'both'")
     if local_eval not in (None, 'global', 'own', 'both'):
         raise ValueError("local_eval must be None, 'global', 'own' or 'both'")
-    known = NAMES + EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM + EXTRA_RFA + EXTRA_TOPK
+    known = NAMES + EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM + EXTRA_RFA + EXTRA_TOPK + EXTRA_DP
     unknown = [n for n in algos if n not in known]
     if unknown:
         raise ValueError('unknown algorithm(s) %s (known: %s)' % (', '.join(unknown), ', '.join(known)))
     names = list(NAMES) + [n for n in EXTRA + EXTRA_FAIR + EXTRA_ROBUST + EXTRA_KRUM + EXTRA_RFA + EXTRA_TOPK
-                           if n in algos]
+                           + EXTRA_DP if n in algos]
     lwant = {None: (), 'both': ('global', 'own')}.get(local_eval, (local_eval,))
     want = {None: (), 'both': ('test', 'val')}.get(client_eval, (client_eval,))
     cev = {'client_%s_%s' % (w, m): [None] * len(names) for w in want for m in ('loss', 'acc')}
@@ -335,6 +338,26 @@ def run(dataset='a9a', D=2000, num_partitions=10, local_epoch=2, Round=100, batc
             keep_participants(name, st)
             k = names.index(name)
             train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
+        for name in EXTRA_DP:
+            if name not in algos:
+                continue
+            # FedAvg's arguments; clients are always parallel.  The --dp-* flags, and the --byzantine-* flags
+            st = ce(name, False)
+            if participation is not None:
+                st = st or {}
+            dpar = dict(kw) if participation is None else dict(participation=participation, sample_seed=sample_seed,
+                                                               **kw)
+            dpar.update(clip=dp_clip, noise_multiplier=dp_noise_multiplier, noise_seed=dp_noise_seed,
+                        weighting=dp_weighting)
+            if dp_adaptive_quantile is not None:
+                dpar['adaptive'] = dict(quantile=dp_adaptive_quantile, lr=dp_adaptive_lr)
+            if byzantine_fraction > 0:
+                dpar['byzantine'] = dict(fraction=byzantine_fraction, attack=byzantine_attack, scale=byzantine_scale)
+            r = timed(name, lambda: getattr(tools, name)(*a, task, C, D, lr, local_epoch, batch_size, False, 0, False,
+                                                         0, Round, stats=st, **dpar))
+            keep_participants(name, st)
+            k = names.index(name)
+            train_mat[k, :, t], error_mat[k, :, t], acc_mat[k, :, t] = r[0].numpy(), r[1].numpy(), r[2].numpy()
         for k, st in calls:
             for key in cev:
                 if key in st:
@@ -368,7 +391,7 @@ def main(argv=None):
     ap.add_argument('--mode', default='sequential', choices=['sequential', 'parallel'])
     ap.add_argument('--algos', default=','.join(NAMES),
                     help='comma-separated; FedNova (exp.py:124, commented out there), Scaffold, FedAvgM, FedAdagrad, '
-                         'FedAdam, FedYogi, QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA and FedTopK run only when named here')
+                         'FedAdam, FedYogi, QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA, FedTopK and DPFedAvg run only when named here')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--client-eval', default=None, choices=['test', 'val', 'both'],
                     help="score every client's local model each round on the test / validation rows")
@@ -377,7 +400,7 @@ def main(argv=None):
     ap.add_argument('--participation', type=float, default=None, metavar='F',
                     help='partial client participation: the fraction of the clients sampled per round, in (0, 1]. '
                          'Applies to the FedAvg, FedProx, FedNova, Scaffold, server-optimizer (FedAvgM, FedAdagrad, '
-                         'FedAdam, FedYogi), QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA and FedTopK calls only, which then run with parallel clients '
+                         'FedAdam, FedYogi), QFedAvg, FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA, FedTopK and DPFedAvg calls only, which then run with parallel clients '
                          'whatever --mode says; the other algorithms are unchanged')
     ap.add_argument('--sample-seed', type=int, default=0, metavar='S',
                     help='seed of the participation sampler (a private generator; with --participation)')
@@ -405,8 +428,20 @@ def main(argv=None):
                     help='FedTopK: the fraction of the C * D values every client uploads per round, in (0, 1]')
     ap.add_argument('--topk-no-memory', action='store_true',
                     help='FedTopK: drop what is not uploaded instead of keeping it in the client residual')
+    ap.add_argument('--dp-clip', type=float, default=1.0, metavar='S',
+                    help='DPFedAvg: the norm every client update is clipped to (inf: no clipping)')
+    ap.add_argument('--dp-noise-multiplier', type=float, default=1.0, metavar='Z',
+                    help='DPFedAvg: the noise multiplier z; the noise on the aggregate has standard deviation '
+                         'z * S * max q (0: clipping only).  A simulator: no privacy accountant is provided')
+    ap.add_argument('--dp-noise-seed', type=int, default=0, metavar='S', help='DPFedAvg: the seed of the device noise')
+    ap.add_argument('--dp-weighting', default='uniform', choices=['size', 'uniform'],
+                    help='DPFedAvg: the client weights q_k, 1 / M or n_k / n')
+    ap.add_argument('--dp-adaptive-quantile', type=float, default=None, metavar='G',
+                    help='DPFedAvg: adapt the clip to this quantile of the update norms (default: a fixed clip)')
+    ap.add_argument('--dp-adaptive-lr', type=float, default=0.2, metavar='ETA',
+                    help='DPFedAvg: the learning rate of the adaptive clip')
     ap.add_argument('--byzantine-fraction', type=float, default=0.0, metavar='F',
-                    help='FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA: the share of the clients that misbehave (0: none)')
+                    help='FedMedian, FedTrimmedMean, Krum, MultiKrum, FedRFA, DPFedAvg: the share of the clients that misbehave (0: none)')
     ap.add_argument('--byzantine-attack', default='sign_flip', choices=['sign_flip', 'gaussian', 'nan'],
                     help='what the misbehaving clients return')
     ap.add_argument('--byzantine-scale', type=float, default=1.0, help='the scale of sign_flip and gaussian')
@@ -419,7 +454,9 @@ def main(argv=None):
               robust_trim=a.robust_trim, byzantine_fraction=a.byzantine_fraction, byzantine_attack=a.byzantine_attack,
               byzantine_scale=a.byzantine_scale, krum_f=a.krum_f, rfa_iters=a.rfa_iters, rfa_nu=a.rfa_nu,
               rfa_init=a.rfa_init, rfa_weighting=a.rfa_weighting, topk_ratio=a.topk_ratio,
-              topk_memory=not a.topk_no_memory)
+              topk_memory=not a.topk_no_memory, dp_clip=a.dp_clip, dp_noise_multiplier=a.dp_noise_multiplier,
+              dp_noise_seed=a.dp_noise_seed, dp_weighting=a.dp_weighting,
+              dp_adaptive_quantile=a.dp_adaptive_quantile, dp_adaptive_lr=a.dp_adaptive_lr)
     for k, name in enumerate(out['name']):
         print('%-15s final test acc %s' % (name, np.round(out['test_acc'][k, -1, :], 2)))
     print('heterogeneity', out['heterogeneity'], 'seconds', {k: np.round(v, 3) for k, v in out['seconds'].items()})

@@ -543,6 +543,38 @@ def topk_count(ratio, C, D):
     return max(1, int(math.floor(float(ratio) * n)))
 
 
+def _check_dp(clip, noise_multiplier, noise_seed, weighting, adaptive, clients='parallel'):
+    """DPFedAvg's keyword checks (host only: before any device is touched)."""
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+    if not real(clip) or not float(clip) > 0.0:
+        raise ValueError('clip must be a number > 0 (inf: no clipping)')
+    if not real(noise_multiplier) or not (0.0 <= float(noise_multiplier) < math.inf):
+        raise ValueError('noise_multiplier must be finite and >= 0')
+    if float(noise_multiplier) > 0.0 and math.isinf(float(clip)):
+        raise ValueError('noise_multiplier > 0 needs a finite clip')
+    if isinstance(noise_seed, bool) or not isinstance(noise_seed, (int, np.integer)) or not 0 <= noise_seed < 2 ** 64:
+        raise ValueError('noise_seed must be an int in [0, 2^64)')
+    if weighting not in SCAFFOLD_WEIGHTINGS:
+        raise ValueError("weighting must be 'size' or 'uniform'")
+    if adaptive is not None:
+        if not isinstance(adaptive, dict) or set(adaptive) - {'quantile', 'lr', 'count_noise'} \
+                or not {'quantile', 'lr'} <= set(adaptive):
+            raise ValueError('adaptive must be None or dict(quantile=, lr=, count_noise=)')
+        if not all(real(v) for v in adaptive.values()):
+            raise ValueError('adaptive: quantile, lr and count_noise must be numbers')
+        if not 0.0 <= float(adaptive['quantile']) <= 1.0:
+            raise ValueError('adaptive: quantile must be in [0, 1]')
+        if not 0.0 <= float(adaptive['lr']) < math.inf:
+            raise ValueError('adaptive: lr must be finite and >= 0')
+        if not 0.0 <= float(adaptive.get('count_noise', 0.0)) < math.inf:
+            raise ValueError('adaptive: count_noise must be finite and >= 0')
+        if math.isinf(float(clip)):
+            raise ValueError('adaptive needs a finite clip')
+    if clients != 'parallel':
+        raise ValueError("DPFedAvg needs clients='parallel': a chained client's W_j - W_g holds its predecessors' work")
+
+
 def byzantine_plan(N, byzantine):
     """``byzantine=`` checked and resolved (host only): None, or (sorted int64 ids, attack, scale, seed).
     ``ids``: the client ids given; ``fraction``: floor(fraction * N) ids fixed once from ``seed``
@@ -588,9 +620,19 @@ class Federation:
                  batch_size, prox, mu, lambda_reg_if, lambda_reg, round, lr_p, clients, stats=None, verbose=True,
                  shuffle_device=True, options=None, participation=None, sample_seed=0, variant='reference',
                  server_lr=1.0, weighting='size', server_opt=None, qffl=None, robust=None, krum=None, rfa=None,
-                 topk=None):
+                 topk=None, dp=None):
         self.robust = algo == 'fedrobust'
         self.byz = None
+        self.dp = algo == 'dpfedavg'
+        if self.dp:
+            # dp: dict(clip=, noise_multiplier=, noise_seed=, adaptive=, byzantine=) (tools.DPFedAvg); weighting
+            # is the keyword above
+            dpk = dict(dp or {})
+            self.dp_clip0, self.dp_z = dpk.get('clip', 1.0), dpk.get('noise_multiplier', 1.0)
+            self.dp_seed, self.dp_adaptive = dpk.get('noise_seed', 0), dpk.get('adaptive')
+            _check_dp(self.dp_clip0, self.dp_z, self.dp_seed, weighting, self.dp_adaptive, clients)
+            self.dp_uniform = weighting == 'uniform'
+            self.byz = byzantine_plan(len(y_train), dpk.get('byzantine'))
         self.topk = algo == 'fedtopk'
         if self.topk:
             # topk: dict(ratio=, error_feedback=) (tools.FedTopK)
@@ -668,7 +710,7 @@ class Federation:
         self.sched = None
         if participation is not None:
             if algo not in ('fedavg', 'fedprox', 'fednova', 'scaffold', 'fedopt', 'qfedavg', 'fedrobust', 'fedkrum',
-                            'fedrfa', 'fedtopk'):
+                            'fedrfa', 'fedtopk', 'dpfedavg'):
                 raise NotImplementedError('participation is implemented for FedAvg, FedProx, FedNova, Scaffold, '
                                           'FedOpt, QFedAvg and FedRobust only')
             if self.chained:
@@ -709,6 +751,9 @@ class Federation:
         if self.topk and nranks > 1:
             # (a client's residual lives with its row; the thresholded fold has no all-reduce form here)
             raise NotImplementedError('FedTopK over more than one torch.distributed rank is not implemented')
+        if self.dp and nranks > 1:
+            # (every update's norm needs its whole row, and the noise is added once)
+            raise NotImplementedError('DPFedAvg over more than one torch.distributed rank is not implemented')
         self.sharded = (not self.chained) and nranks > 1
         if self.sharded and len(y_train) < nranks:
             raise ValueError("clients='parallel' over %d ranks needs at least one client per rank (got %d clients)"
@@ -939,6 +984,16 @@ class Federation:
             self.tk_kept = torch.full((R, self.N), -1, dtype=torch.int32, device=dev)
             self.tk_ws = self.agg.topk_ws()
             self.tk_rnorm = torch.zeros(R, dtype=torch.float64, device=dev) if stats is not None else None
+        if self.dp:
+            # FedAvg's round with fs_aggregate_dp as its aggregate; every round's coefficients, norms and state
+            # land in that round's row of the histories (the setter is called again before each round), the
+            # adaptive clip lives on the device
+            self.dp_c = torch.zeros(R, self.N, dtype=torch.float32, device=dev)
+            self.dp_r = torch.full((R, self.N), float('nan'), dtype=torch.float64, device=dev)
+            self.dp_state = torch.full((R, engine.DP_STATE), float('nan'), dtype=torch.float64, device=dev)
+            self.dp_clip_dev = (torch.full((1,), float(self.dp_clip0), dtype=torch.float64, device=dev)
+                                if self.dp_adaptive is not None else None)
+            self.dp_ws = self.agg.dp_ws()
         self.chunk = 1
         if self.mixture is None and shuffle_device and self.sched is None:   # (subset rounds: per-round slots)
             self.chunk = max(1, min(int(opts['shuffle_chunk']), R))
@@ -1025,6 +1080,9 @@ class Federation:
                               self.rf_b[t], self.rf_obj[t], self.rf_ws)
         if self.topk:
             self.plan.set_topk(True, self.tk_count, self.tk_e, self.tk_tau[t], self.tk_kept[t], self.tk_ws)
+        if self.dp:
+            self.plan.set_dp(True, self.dp_clip0, self.dp_z, self.dp_seed, self.dp_uniform, self.dp_adaptive,
+                             self.dp_clip_dev, self.dp_c[t], self.dp_r[t], self.dp_state[t], self.dp_ws, cols=self.D)
         if self.sched is not None:
             M = len(self.sched[t])
 
@@ -1243,6 +1301,19 @@ class Federation:
                 self.stats['residual_norm'] = self.tk_rnorm[:R].cpu().numpy()
                 if self.tk_e is not None:
                     self.stats['residual'] = self.tk_e[:, :, :D].detach().clone()
+            if self.dp:
+                sh, rh = self.dp_state[:R].cpu().numpy(), self.dp_r[:R].cpu().numpy()
+                norms = np.full((R, self.N), np.nan)
+                for t in range(R):
+                    S = np.arange(self.N) if self.sched is None else self.sched[t]
+                    norms[t, S] = rh[t, :len(S)]
+                self.stats['dp_clip'], self.stats['dp_sigma'] = sh[:, 0].copy(), sh[:, 1].copy()
+                self.stats['dp_clipped'] = np.array([(self.N if self.sched is None else len(self.sched[t]))
+                                                     for t in range(R)], np.float64) - sh[:, 2] - sh[:, 3]
+                self.stats['dp_dropped'] = sh[:, 3].copy()
+                self.stats['dp_norms'] = norms
+                if self.byz is not None:
+                    self.stats['byzantine_ids'] = self.byz[0].copy()
             if self.mixture is not None:
                 p = self.mixture.p[self.pos_dev] if self.zshard else self.mixture.p
                 self.stats['p'] = p.detach().clone()
@@ -1563,6 +1634,43 @@ def FedTopK(X_train, y_train, X_test, y_test, type='classification', num_classes
                 prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
                 options=options, participation=participation, sample_seed=sample_seed,
                 topk=dict(ratio=ratio, error_feedback=error_feedback))
+
+
+def DPFedAvg(X_train, y_train, X_test, y_test, type='classification', num_classes=10, D=200, lr=0.01, epoch=2,
+             batch_size=32, prox=False, mu=0.1, lambda_reg_if=False, lambda_reg=0.01, round=100, *, clip=1.0,
+             noise_multiplier=1.0, noise_seed=0, weighting='uniform', adaptive=None, byzantine=None, stats=None,
+             verbose=True, options=None, participation=None, sample_seed=0):
+    """DP-FedAvg: user-level differential privacy by per-client norm clipping and Gaussian noise on the aggregate
+    (McMahan, Ramage, Talwar & Zhang, ICLR 2018; Geyer, Klein & Nabi 2017; not in the reference): FedAvg's
+    positional list, clients always parallel.  Local training is FedAvg's launch unchanged -- both tasks,
+    ``prox=True``, any ``batch_size`` the task's trainer accepts, ``participation`` -- and the server step is
+    fs_aggregate_dp: every sampled client's update W_k - W_g is scaled to a norm of at most ``clip`` (S), the
+    clipped updates are folded onto ``W_g`` with the weights q_k (``weighting='uniform'``: 1 / M, the
+    fixed-denominator estimator; ``'size'``: FedAvg's p_k / sum_S p), and Gaussian noise of standard deviation
+    ``noise_multiplier * clip * max_k q_k`` is added from a counter-based generator on the device
+    (Philox4x32-10 keyed by ``noise_seed``, counted by round and position: the same bits on every run).  An
+    update whose norm is not finite (it holds a NaN or an Inf, or its squares overflow) is dropped and counted.
+    ``clip=inf, noise_multiplier=0`` is ``FedAvgM(server_lr=1.0, beta1=0.0)`` bit for bit (size weighting).
+    ``adaptive=dict(quantile=, lr=, count_noise=)``: the clip follows the ``quantile`` of the update norms
+    (Andrew, Thakkar, McMahan & Ramaswamy, NeurIPS 2021), S <- S exp(-lr ((b + count_noise g) / M - quantile))
+    with b the number of unclipped updates, on the device; the noise of a round uses that round's S.
+    ``byzantine=``: as ``FedRFA``'s -- norm clipping bounds one client's influence (Sun et al. 2019).
+    This is a simulator: the noise is floating-point Gaussian with a truncated tail (|g| < 6.77), not a deployed
+    mechanism's, and NO PRIVACY ACCOUNTANT is provided.  ``participation`` samples a fixed-size subset without
+    replacement, to which the Poisson-subsampled RDP bounds do not apply as they stand; the stats carry what an
+    external accountant needs (the noise multiplier, M_t / N, the rounds).  The global generator is consumed
+    exactly as by ``FedAvg(clients='parallel')`` with the same ``participation``, and ``train_loss`` is FedAvg's.
+    Stats, float64 on the CPU: ``stats['dp_clip']`` [R] (the round's S), ``stats['dp_sigma']`` [R],
+    ``stats['dp_norms']`` [R, N] (the update norms; NaN where a client was not sampled), ``stats['dp_clipped']``
+    [R] (updates scaled down) and ``stats['dp_dropped']`` [R].  ValueError for a bad keyword;
+    NotImplementedError over more than one torch.distributed rank."""
+    _check_dp(clip, noise_multiplier, noise_seed, weighting, adaptive)
+    byzantine_plan(len(y_train), byzantine)
+    return _run('dpfedavg', X_train, y_train, X_test, y_test, None, type, num_classes, D, lr, epoch, batch_size,
+                prox, mu, lambda_reg_if, lambda_reg, round, None, 'parallel', stats=stats, verbose=verbose,
+                options=options, participation=participation, sample_seed=sample_seed, weighting=weighting,
+                dp=dict(clip=clip, noise_multiplier=noise_multiplier, noise_seed=noise_seed, adaptive=adaptive,
+                        byzantine=byzantine))
 
 
 def FedAMW(X_train, y_train, X_test, y_test, validloader, type='classification', num_classes=10, D=200, lr=0.01,
